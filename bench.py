@@ -4,10 +4,12 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full       (+ the secondary legs: roofline, other workloads, CPU baseline, ...)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   (+ DIR/<name>.npy: what the last timed step computed)
 
 One step = one pass of the hot path over one minibatch: index tensors (resident in HBM when the timed region starts: one
 device-to-device copy into the step's input buffers) -> encoder -> reparameterise -> GRU decoder -> tied logits ->
-CE + beta*KL -> full backward -> (RCCL gradient all-reduce when N>1) -> fused Adam.  `ms_per_step_with_upload` is the same
+CE + beta*KL -> full backward -> (RCCL gradient all-reduce when N>1) -> fused Adam.  `ms_per_step_with_upload` (--full) is the same
 step fed from pinned host memory (one host -> device copy per step on the dependent chain: the figure of rounds 1-4).  Weak scaling: 1024 graphs per GPU per step
 (BASELINE.json configs[1]: autoreg_syn-paths, model_type SAIL, batch 1024, D=512 Z=10 n=3).
 Prints ONE JSON line on rank 0.
@@ -66,6 +68,27 @@ PMC_FILE = "profiles/r05_pmc_summary.json"   # committed PMC passes of this comm
 
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs writes at most this much array data (64 MB in all with the .npy headers)
+
+
+def dump_outputs(outdir, outputs):
+    """--dump-outputs DIR: what the last timed step computed, one float32 DIR/<name>.npy per array -- `loss` = the
+    step's out4 [loss, ce, kl, token-loss sum], `params` = every parameter after the step's Adam update (the flat fp32
+    vector Engine.P).  An array that would take the total past DUMP_BYTES is replaced by a fixed, seeded sample of its
+    elements (sorted indices: the same ones in every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    room = DUMP_BYTES
+    for name, t in outputs.items():
+        a = t.detach().cpu().float().numpy()
+        if a.nbytes > room:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, room // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+            log(f"--dump-outputs: {name} sampled, {a.size} of {t.numel()} elements")
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        room -= a.nbytes
 
 
 def flops_per_graph(cfg):
@@ -217,9 +240,11 @@ def diag_byte_models(eng, B):
 
 
 def time_workload(dev, workload, precision, dropout, batch, steps, warmup, settle, extra_cfg=None, world=1, rank=0, dist=None,
-                  use_dp=False, no_graph=False):
+                  use_dp=False, no_graph=False, upload_leg=True, keep_outputs=False):
     """K timed train steps of one workload preset on this rank's GPU (the contract's timed region: barrier + synchronize on
-    both sides, max over ranks); returns the engine and the timing."""
+    both sides, max over ranks); returns the engine and the timing.  `upload_leg`: also time the PCIe-fed steps
+    (`dt_upload`, K >= 100 only); `keep_outputs`: host copies of what the last timed step returned -- out4 and the
+    parameters after its Adam update -- taken before anything else runs on the engine (`outputs`)."""
     import torch
     from ark_amd.engine import Engine
     from ark_amd import initlib
@@ -312,8 +337,11 @@ def time_workload(dev, workload, precision, dropout, batch, steps, warmup, settl
         dt = time.perf_counter() - t0
         eng.raise_on_sweep_error()   # a persistent sweep that gave up waiting voids the run
         loss_k = [float(x) for x in out4.cpu()]   # (of the K timed steps: the secondary leg below trains on)
+        outputs = None
+        if keep_outputs:
+            outputs = {"loss": out4.detach().cpu().clone(), "params": eng.P.detach().cpu().clone()}
         dt_up = None
-        if dist is None and not use_dp and steps >= 100:
+        if upload_leg and dist is None and not use_dp and steps >= 100:
             # the same steps fed over PCIe (pinned host -> device per step, on the dependent chain): a secondary figure, never `value`
             nup = min(steps, 300)
             for i in range(max(50, settle)):   # (the steps after the change of feed run slower for a while, as after a capture: not timed)
@@ -331,7 +359,7 @@ def time_workload(dev, workload, precision, dropout, batch, steps, warmup, settl
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     return {"eng": eng, "cfg": cfg, "B": B, "Bg": Bg, "dt": dt, "loss": loss_k,
-            "h2d_bytes": n_tri + n_seq + n_eps, "steps": steps, "dt_upload": dt_up, "eager": eager}
+            "h2d_bytes": n_tri + n_seq + n_eps, "steps": steps, "dt_upload": dt_up, "eager": eager, "outputs": outputs}
 
 
 def other_workloads(dev, precision, dropout, mfma_peak):
@@ -516,6 +544,12 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL, one GPU per rank (the measured configuration); gloo = functional rehearsal, ranks may share a GPU")
     ap.add_argument("--wgrad", default="", help="weight-gradient kernel choices, e.g. tile=128,nbuf=2,target_wgs=300,balance=1")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs: PCIe-fed steps, diagonal-kernel timings + roofline, the one-rank data-parallel "
+                         "schedule, the other workloads, the Transformer variants, CPU baseline and ELBO parity (--no-other, "
+                         "--no-cpu-baseline drop some of them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, 64 MB at most)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -557,16 +591,19 @@ def main():
         extra["ark_wgrad_tuning"] = {k: int(v) for k, v in (kv.split("=") for kv in args.wgrad.split(","))}
     use_dp = world > 1 or args.force_dist
     run = time_workload(dev, args.workload, args.precision, args.dropout, args.batch, args.steps, args.warmup, args.settle, extra,
-                        world=world, rank=rank, dist=dist, use_dp=use_dp, no_graph=args.no_graph)
+                        world=world, rank=rank, dist=dist, use_dp=use_dp, no_graph=args.no_graph, upload_leg=args.full,
+                        keep_outputs=bool(args.dump_outputs) and rank == 0)
     eng, cfg, B, Bg, dt, loss, h2d_bytes = (run[k] for k in ("eng", "cfg", "B", "Bg", "dt", "loss", "h2d_bytes"))
     log(f'timed {args.steps} steps in {dt:.3f}s loss={loss[0]:.4f}')
+    if run["outputs"] is not None:
+        dump_outputs(args.dump_outputs, run["outputs"])
 
     if rank == 0:
         gps = Bg * args.steps / dt
         fl = flops_per_graph(cfg)
         mfma_peak = 2500.0 if args.precision != "f32" else 157.3
         roof = None
-        if eng.ws["v2"]:
+        if args.full and eng.ws["v2"]:
             times = time_diag_kernels(eng, B)
             models = diag_byte_models(eng, B)
             traffic = {}
@@ -643,7 +680,7 @@ def main():
             "model_mfma_frac": gps * fl / 1e12 / mfma_peak,
             "roofline": roof,
         }
-        if not args.no_other and world == 1 and args.workload == "syn-paths" and not args.force_dist:
+        if args.full and not args.no_other and world == 1 and args.workload == "syn-paths" and not args.force_dist:
             del eng
             torch.cuda.empty_cache()
             res["dp_overhead_1rank"] = dp_overhead_1rank(dev, args, extra, dt / args.steps * 1e3)
@@ -651,7 +688,7 @@ def main():
             res["dp_overhead_1rank"].update(dp_overhead_sweep_workloads(args, res["other_workloads"]))
             if args.precision != "f32":
                 res["transformer_variants"] = transformer_variants(dev, args.precision, args.dropout)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(cfg, B, steps=args.cpu_steps, warmup=5)
             if args.workload == "syn-paths":
                 try:

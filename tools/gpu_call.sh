@@ -12,7 +12,7 @@ rc=$?
 tail -15 "$O/${TAG}_tests.log"
 echo "pytest rc=$rc"
 if [ $rc -ge 124 ]; then exit $rc; fi
-timeout -k 10 300 python bench.py --no-other --no-cpu-baseline --steps 500 > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || { echo "bench failed"; tail -5 "$O/${TAG}_bench.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --no-other --no-cpu-baseline --steps 500 > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || { echo "bench failed"; tail -5 "$O/${TAG}_bench.err"; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/${TAG}_bench.json"))
