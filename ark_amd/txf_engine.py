@@ -14,8 +14,8 @@ Same division of labour as ark_amd.engine.Engine, whose optimiser / step-scalar 
 inherits: flat fp32 parameter, gradient and Adam-moment buffers, time-major activations (row (t, b) = t*B + b, so the token
 gather, vocabulary projection, cross-entropy and latent kernels are the GRU models'), every op a hand-written gfx950
 kernel behind the C-ABI (csrc/txf.hip: residual + LayerNorm, masked / causal attention, the uniform cross-attention of the
-repeated memory, counter-hash dropout; csrc/gemm.hip: the dense products, exact fp32 or 16-bit MFMA operands).  No torch
-arithmetic, no CPU fallback.
+repeated memory, counter-hash dropout; csrc/gemm.hip: the dense products, exact fp32 or 16-bit MFMA operands; csrc/attn_decode.hip: the single-query attention of
+one-token generation over per-layer K/V caches).  No torch arithmetic, no CPU fallback.
 """
 from collections import OrderedDict
 
@@ -165,6 +165,9 @@ class TxfEngine(Engine):
         self.fast_gemm = bool(cfg.get("ark_txf_fast_gemm", True)) and self.prec_fwd != L.PREC_F32
         # self-attention longer than 16 positions on the matrix cores, flash style (no [B, H, L, L] arrays): csrc/attn_mfma.hip
         self.flash = bool(cfg.get("ark_txf_flash", True))
+        # generation advances ONE token per step over per-layer K/V caches (decode_begin / decode_step; csrc/attn_decode.hip);
+        # 0: the prefix re-run of the reference (prefix_logits per generated token), kept as the checker
+        self.kv_cache = bool(cfg.get("ark_txf_kv_cache", True))
         # large vocabularies: output projection FUSED with the cross-entropy (csrc/vocab_ce.hip, as in the GRU engine): the
         # [B*L, V] logits and their gradient never exist in the train / eval-loss steps (2.5 GB at wd-articles)
         self.fused_ce = bool(cfg.get("ark_fused_ce", self.prec_fwd != L.PREC_F32 and self.V >= 2048 and self.D in (64, 128, 256, 512)))
@@ -334,7 +337,9 @@ class TxfEngine(Engine):
               one(prec, ctypes.c_int), one(R, ctypes.c_int), L.cur_stream())
         return out
 
-    def _gemm(self, a_lay, b_lay, epi, A, lda, Bm, ldb, C, ldc, M, N, K, C2=None, bias=None, aux=None, acc=0):
+    def _gemm(self, a_lay, b_lay, epi, A, lda, Bm, ldb, C, ldc, M, N, K, C2=None, bias=None, aux=None, acc=0, B16=None):
+        """B16 (optional): the 16-bit copy of a [N, K] weight `Bm` made earlier in this precision (decode_begin: the weights do
+        not change between the steps of one generation); only the fast product reads it"""
         KM, MM = L.LAY_KMAJ, L.LAY_MMAJ
         pr = self.prec
         if getattr(self, "_prepared", None) is not None and self._prepared != A.data_ptr():
@@ -347,7 +352,8 @@ class TxfEngine(Engine):
         if a_lay == KM and K % 64 == 0 and lda == K and ((b_lay == KM and ldb == K) or (b_lay == MM and ldb == N)):
             # C[M,N] (+)= A[M,K] op(B): B is [N,K] (KM) or [K,N] (MM: its transposed 16-bit copy is made)
             A16 = self._cast("a", A, M * K, pr)
-            B16 = self._cast("b", Bm, N * K, pr) if b_lay == KM else self._cast_t("b", Bm, K, N, pr)
+            if B16 is None or b_lay != KM:
+                B16 = self._cast("b", Bm, N * K, pr) if b_lay == KM else self._cast_t("b", Bm, K, N, pr)
             if acc and epi == L.EPI_NONE and ldc == N:   # C += A op(B) in the product's own epilogue
                 _call("ark_gemm16", L.i32(pr), L.i32(L.EPI_ADD), L.ptr(A16), L.i64(K), L.ptr(B16), L.i64(K), L.ptr(C), L.i64(ldc),
                       L.ptr(None), L.ptr(None), L.i32(M), L.i32(N), L.i32(K), L.i32(0), st)
@@ -906,11 +912,196 @@ class TxfEngine(Engine):
             self.training = was
         return self._logits(w)[(t - 1) * B:t * B, :self.V]
 
-    def decode_begin(self, *a, **k):
-        raise L.ArkError(f"{self.mt} has no incremental decoder state: use prefix_logits()")
+    # ------------------------------------------------------------------ incremental decode over K/V caches
+    def _decode_ws(self, B):
+        """persistent state of the one-token-at-a-time decoder, per batch size (as Engine._decode_ws; apart from the training
+        and the prefix workspaces): per layer ONE fp32 cache kv [seq_len*B, 2D] of time-major rows (t, b) = k | v -- fp32 in
+        every precision mode -- and [B, .] step buffers that all layers share.  Nothing here grows with L*L, and nothing is
+        allocated per step.  At most two batch sizes are kept (a cache is seq_len*B*2D floats per layer); a state that was
+        handed out stays valid after it leaves this table"""
+        ws = self.__dict__.setdefault("_kv_cache_ws", {})
+        d = ws.get(B)
+        if d is None:
+            dev, D, n = self.device, self.D, self.n
+            f = lambda *sh: torch.zeros(*sh, device=dev, dtype=torch.float32)
+            d = {"B": B, "kv": [f(self.seq_len * B, 2 * D) for _ in range(n)], "x0": f(B, D), "q": f(B, D), "att": f(B, D),
+                 "sa": f(B, D), "s": f(B, D), "st": f(B, 2), "x1": f(B, D), "x2": f(B, D), "x3": f(B, D), "f": f(B, FF),
+                 "g2": f(B, D), "logits": f(B, self.ldl), "nxt": torch.zeros(B, dtype=torch.int64, device=dev),
+                 "toks": torch.zeros(B, self.seq_len, dtype=torch.int64, device=dev)}
+            if self.vae:
+                d.update({"z": f(B, self.Z), "mem": f(B, D), "vmem": f(B, D), "ca": [f(B, D) for _ in range(n)]})
+            if len(ws) >= 2:
+                ws.pop(next(iter(ws)))
+            ws[B] = d
+        return d
+
+    def _decode_weights(self):
+        """(key, [N, K] weight) of every product of decode_step"""
+        p, D = self.p, self.D
+        for l in range(self.n):
+            pre = f"dec.txf.layers.{l}."
+            w_in = p[pre + "self_attn.in_proj_weight"]
+            yield (l, "q"), w_in[:D]
+            yield (l, "kv"), w_in[D:]
+            yield (l, "o"), p[pre + "self_attn.out_proj.weight"]
+            yield (l, "f1"), p[pre + "linear1.weight"]
+            yield (l, "f2"), p[pre + "linear2.weight"]
+        yield "out", p["dec.out.weight"]
+
+    def _decode_w16(self):
+        """16-bit precisions on the fast products: the 16-bit copies of the decoder's weights, cast ONCE per generation instead
+        of once per product and token (the same cast, so the same values: at wd-articles the output weight alone is 31 M
+        elements, ~190 MB of traffic per token otherwise).  One set per engine, refreshed by every decode_begin."""
+        w16 = self.__dict__.setdefault("_dec_w16", {})
+        if not (self.fast_gemm and self.prec_fwd != L.PREC_F32):
+            return {}
+        for key, w in self._decode_weights():
+            N, K = w.shape
+            if K % 64 == 0:
+                if key not in w16:
+                    w16[key] = torch.empty(N * K, device=self.device, dtype=torch.int16)
+                _call("ark_cast16", L.i32(self.prec_fwd), L.ptr(w), L.ptr(w16[key]), L.i64(N * K), L.cur_stream())
+        return w16
+
+    @torch.no_grad()
+    def decode_begin(self, B, z=None):
+        """start an incremental decode of B sequences (mirrors Engine.decode_begin).  t-SAIL: mem = z_proj(z), and per layer
+        the cross-attention term ca_l = out_proj_l(v_proj_l(mem)) ONCE: the memory is the same row at every position, so in eval
+        mode the context is the value row itself, whatever the query and the position are (_cross_attn_fwd)."""
+        self.prec = self.prec_fwd
+        d = self._decode_ws(B)
+        d["w16"] = self._decode_w16()
+        if self.vae:
+            if z is None:
+                raise L.ArkError("t-SAIL decode_begin needs the latents z [B, Z]")
+            KM, p, D, Z = L.LAY_KMAJ, self.p, self.D, self.Z
+            d["z"].copy_(z.to(self.device, dtype=torch.float32))
+            self._gemm(KM, KM, L.EPI_BIAS, d["z"], Z, p["dec.z_proj.weight"], Z, d["mem"], D, B, D, Z, bias=p["dec.z_proj.bias"])
+            for l in range(self.n):
+                a = f"dec.txf.layers.{l}.multihead_attn."
+                self._gemm(KM, KM, L.EPI_BIAS, d["mem"], D, p[a + "in_proj_weight"][2 * D:], D, d["vmem"], D, B, D, D,
+                           bias=p[a + "in_proj_bias"][2 * D:])
+                self._gemm(KM, KM, L.EPI_BIAS, d["vmem"], D, p[a + "out_proj.weight"], D, d["ca"][l], D, B, D, D,
+                           bias=p[a + "out_proj.bias"])
+        return d
+
+    @torch.no_grad()
+    def decode_step(self, d, cur, t):
+        """advance the causal decoder by ONE token: `cur` [B] int64 are the tokens at position t; returns the logits [B, V] of
+        position t + 1 (a view of the persistent buffer).  Every product runs on B rows; the new position's k | v rows are
+        written by their product straight into rows t*B .. t*B+B-1 of each layer's cache, and its query attends to cache rows
+        0 .. t (ark_attn_decode_fwd, exact fp32).  The products follow the engine's forward precision, as prefix_logits does.
+        Replaces the reference's re-run of the whole prefix per generated token (models.py:291, 430)."""
+        B, D, n, V = d["B"], self.D, self.n, self.V
+        if cur.shape[0] != B or not 0 <= t < self.seq_len:
+            raise L.ArkError(f"decode_step: {cur.shape[0]} tokens at position {t} for a state of {B} rows, {self.seq_len} positions")
+        self.prec = self.prec_fwd
+        KM, p, w16 = L.LAY_KMAJ, self.p, d["w16"]
+        st = L.cur_stream()
+        _call("ark_tok_gather", L.ptr(cur), L.i64(1), L.ptr(p["dec.tok_emb.weight"]), L.ptr(p["dec.pos_emb.weight"][t:]),
+              L.ptr(d["x0"]), L.i32(B), L.i32(1), L.i32(D), L.ptr(None), st)
+        x = d["x0"]
+        for l in range(n):
+            pre = f"dec.txf.layers.{l}."
+            a = pre + "self_attn."
+            w_in, b_in = p[a + "in_proj_weight"], p[a + "in_proj_bias"]
+            kv = d["kv"][l]
+            self._gemm(KM, KM, L.EPI_BIAS, x, D, w_in[:D], D, d["q"], D, B, D, D, bias=b_in[:D], B16=w16.get((l, "q")))
+            self._gemm(KM, KM, L.EPI_BIAS, x, D, w_in[D:], D, kv[t * B:], 2 * D, B, 2 * D, D, bias=b_in[D:],
+                       B16=w16.get((l, "kv")))
+            _call("ark_attn_decode_fwd", L.ptr(d["q"]), L.ptr(kv), L.ptr(d["att"]), L.i32(B), L.i32(t + 1), L.i32(D), L.i32(self.H), st)
+            self._gemm(KM, KM, L.EPI_BIAS, d["att"], D, p[a + "out_proj.weight"], D, d["sa"], D, B, D, D, bias=p[a + "out_proj.bias"],
+                       B16=w16.get((l, "o")))
+            self._ln_fwd(x, d["sa"], pre + "norm1", d["s"], d["x1"], d["st"], B, D)
+            x = d["x1"]
+            if self.vae:
+                self._ln_fwd(x, d["ca"][l], pre + "norm2", d["s"], d["x2"], d["st"], B, D)
+                x = d["x2"]
+            self._gemm(KM, KM, L.EPI_BIAS_RELU, x, D, p[pre + "linear1.weight"], D, d["f"], FF, B, FF, D, bias=p[pre + "linear1.bias"],
+                       B16=w16.get((l, "f1")))
+            self._gemm(KM, KM, L.EPI_BIAS, d["f"], FF, p[pre + "linear2.weight"], FF, d["g2"], D, B, D, FF, bias=p[pre + "linear2.bias"],
+                       B16=w16.get((l, "f2")))
+            self._ln_fwd(x, d["g2"], pre + ("norm3" if self.vae else "norm2"), d["s"], d["x3"], d["st"], B, D)
+            x = d["x3"]
+        self._gemm(KM, KM, L.EPI_BIAS, x, D, p["dec.out.weight"], D, d["logits"], self.ldl, B, V, D, bias=p["dec.out.bias"],
+                   B16=w16.get("out"))
+        return d["logits"][:, :V]
+
+    @torch.no_grad()
+    def decode_reorder(self, d, j, t):
+        """beam search: block i of the beam axis continues beam j[i].  Gathers the surviving beams' cache blocks of positions
+        0 .. t (rows are (position, beam, b)), as the GRU beam gathers its states; nothing to do when j is the identity"""
+        beam = j.numel()
+        if j.tolist() == list(range(beam)):
+            return
+        for kv in d["kv"]:
+            blk = kv.view(self.seq_len, beam, d["B"] // beam, 2 * self.D)[:t + 1]
+            blk.copy_(blk.index_select(1, j))
 
     @torch.no_grad()
     def greedy_decode(self, z, max_len=None, bos=1, eos=2):
+        """token sequences of SAIL.decode_latent(z, beam=1) for t-SAIL (reference models.py:282-300): argmax of the next
+        position, stop once every row ends in EOS.  One token per step over the K/V caches; as Engine.greedy_decode, every step
+        is queued without a host round trip and the stopping rule (first position at which EVERY row's token is EOS) is applied
+        once at the end -- positions up to there do not depend on later ones.  `ark_txf_kv_cache: 0`: the prefix re-run."""
+        assert self.vae
+        if not self.kv_cache:
+            return self._greedy_decode_prefix(z, max_len, bos, eos)
+        B = z.shape[0]
+        Lmax = (self.seq_len - 1) if max_len is None else max_len
+        d = self.decode_begin(B, z)
+        toks = d["toks"]
+        toks.fill_(eos)
+        toks[:, 0] = bos
+        st = L.cur_stream()
+        for t in range(Lmax):
+            self.decode_step(d, toks[:, t].contiguous() if t == 0 else d["nxt"], t)
+            _call("ark_argmax_rows", L.ptr(d["logits"]), L.i64(self.ldl), L.ptr(d["nxt"]), L.i32(B), L.i32(self.V), st)
+            toks[:, t + 1] = d["nxt"]
+        done = (toks[:, 1:Lmax + 1] == eos).all(dim=0)          # ONE synchronisation, after the last step
+        hit = torch.nonzero(done)
+        stop = int(hit[0]) + 1 if hit.numel() else Lmax
+        return toks[:, :stop + 1].clone()
+
+    @torch.no_grad()
+    def beam_decode(self, z, beam, max_len=None, bos=1, eos=2):
+        """the reference's batch-shared beam (models.py:282-300): candidates ranked by the batch-MEAN accumulated
+        log-probability (stable descending sort), stop when every kept beam ends in EOS everywhere.  beam x B rows of ONE
+        incremental decode, with the ranking and stopping logic of Engine.beam_decode; the surviving beams' cache blocks are
+        gathered by decode_reorder.  `ark_txf_kv_cache: 0`: the prefix re-run."""
+        assert self.vae and beam >= 1
+        if not self.kv_cache:
+            return self._beam_decode_prefix(z, beam, max_len, bos, eos)
+        B = z.shape[0]
+        Lmax = (self.seq_len - 1) if max_len is None else max_len
+        zr = z.to(self.device, dtype=torch.float32).repeat(beam, 1)
+        d = self.decode_begin(beam * B, zr)
+        dev = self.device
+        toks = torch.full((beam, B, Lmax + 1), eos, dtype=torch.int64, device=dev)
+        toks[:, :, 0] = bos
+        scores = torch.zeros(beam, B, device=dev)
+        active = 1          # distinct beams so far (all blocks start as copies of the single BOS beam)
+        length = 1
+        for t in range(Lmax):
+            logits = self.decode_step(d, toks[:, :, t].reshape(-1).contiguous(), t)
+            logp = torch.log_softmax(logits.float(), dim=-1).view(beam, B, -1)
+            top_lp, ids = logp.topk(beam, dim=-1)                         # [beam, B, beam]
+            cand = (scores[:, :, None] + top_lp)[:active]                 # candidate (j, k) = beam j extended by its k-th token
+            order = torch.sort(cand.mean(dim=1).reshape(-1), descending=True, stable=True).indices[:beam]
+            j, k = order // beam, order % beam
+            new_tok = ids[j, :, k]                                        # [beam, B]
+            scores = scores[j] + top_lp[j, :, k]
+            toks = toks[j]
+            toks[:, :, t + 1] = new_tok
+            self.decode_reorder(d, j, t)
+            active = beam
+            length = t + 2
+            if bool((new_tok == eos).all()):                                # every beam's last token is EOS
+                break
+        return toks[0, :, :length].clone()
+
+    @torch.no_grad()
+    def _greedy_decode_prefix(self, z, max_len=None, bos=1, eos=2):
         """token sequences of SAIL.decode_latent(z, beam=1) for t-SAIL (reference models.py:282-300): prefix re-run,
         argmax of the last position, stop once every row ends in EOS"""
         assert self.vae
@@ -928,7 +1119,7 @@ class TxfEngine(Engine):
         return s
 
     @torch.no_grad()
-    def beam_decode(self, z, beam, max_len=None, bos=1, eos=2):
+    def _beam_decode_prefix(self, z, beam, max_len=None, bos=1, eos=2):
         """the reference's batch-shared beam (models.py:282-300) on prefix re-runs: candidates ranked by the batch-MEAN
         accumulated log-probability (stable descending sort), stop when every kept beam ends in EOS everywhere"""
         assert self.vae and beam >= 1

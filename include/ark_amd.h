@@ -467,6 +467,12 @@ int ark_attn_flash_fwd(int prec, const float* qkv, float* out, float* lse, const
 int ark_attn_flash_bwd(int prec, const float* qkv, const float* out, const float* lse, const float* dout, float* delta,
                        float* dqkv, const unsigned char* kmask, int B, int L, int D, int n_heads, int causal, float drop_p,
                        uint64_t seed, const float* hyper, void* stream);
+/* One-token decoding over a K/V cache (csrc/attn_decode.hip): the last causal row of ark_attn_fwd without dropout and without
+ * a probabilities array.  q, out [B, D]: the new position's rows; kv [cap*B, 2D] time-major cache rows (t, b) = t*B + b holding
+ * k | v, of which rows 0 .. n_keys-1 (n_keys >= 1) are attended and later ones never read.  Exact fp32 on the vector units,
+ * online softmax in one pass over the cache; any n_keys; dh = D / n_heads a multiple of 4, at most 256.  Replaces the
+ * reference's re-run of the whole prefix per generated token (models.py:291, 430). */
+int ark_attn_decode_fwd(const float* q, const float* kv, float* out, int B, int n_keys, int D, int n_heads, void* stream);
 /* ---- t-SAIL (reference: AutoRegEncoder / AutoRegDecoder, kgvae/model/models.py:66-114) ----------------------------------
  * encoder input rows (t, b) over the TRIPLE index: x = [E[h] | R[r] | E[t]], kmask[b, t] = (r != pad_rid) (nullable) */
 int ark_triple_gather(const int64_t* triples, const float* E, const float* R, float* x, unsigned char* kmask, int B, int T, int D,

@@ -240,8 +240,8 @@ class SAIL(_EngineModel):
     def beam_generate(self, seq_len, special_tokens, seq_to_triples, z, ent_base, rel_base, beam=4):
         eng = self.engine()
         if beam == 1:
-            # beam 1 == greedy argmax per row; the causal GRU is advanced one token per step on
-            # the device instead of re-running the whole prefix
+            # beam 1 == greedy argmax per row; the decoder (causal GRU, or the Transformer over its K/V caches) is
+            # advanced one token per step on the device instead of re-running the whole prefix
             best = eng.greedy_decode(z, max_len=seq_len - 1, bos=special_tokens["BOS"], eos=special_tokens["EOS"]).cpu()
             return [seq_to_triples(row, special_tokens, ent_base, rel_base) for row in best]
         # beam > 1: the reference's batch-shared beam (candidates ranked by the batch-MEAN log-prob); every beam keeps its
@@ -361,8 +361,9 @@ class ARK(_EngineModel):
     def generate(self, seq_len, special_tokens, device=None, batch_size=1, beam=1, sample=False, temperature=1.0,
                  top_p=0.0, top_k=0, host_draws=False):
         """autoregressive generation with the reference's sampling rules (models.py:407-471): greedy, or
-        temperature / top-k / nucleus sampling.  The causal GRU advances ONE token per step on the engine
-        (Engine.decode_step, exact-fp32 kernels) instead of re-running the whole prefix.
+        temperature / top-k / nucleus sampling.  The decoder advances ONE token per step on the engine (the causal GRU:
+        Engine.decode_step, exact-fp32 kernels; t-ARK: TxfEngine.decode_step over K/V caches) instead of re-running the whole
+        prefix.
 
         Draws: with a nucleus the reference draws in SORTED space, one torch.multinomial per row, and maps the drawn
         position back through the sort; otherwise one batched multinomial over the dense distribution.  By default the
@@ -374,11 +375,13 @@ class ARK(_EngineModel):
         B = batch_size
         bos, eos = special_tokens["BOS"], special_tokens["EOS"]
         eng = self.engine()
-        txf = self.config["model_type"] == "t-ARK"   # (no recurrent state: the prefix is re-run, as the reference does)
-        d = None if txf else eng.decode_begin(B)
+        # t-ARK advances one token per step too, over per-layer K/V caches (TxfEngine.decode_step); `ark_txf_kv_cache: 0`
+        # re-runs the whole prefix per token, as the reference does
+        rerun = self.config["model_type"] == "t-ARK" and not eng.kv_cache
+        d = None if rerun else eng.decode_begin(B)
         seq = torch.full((B, 1), bos, dtype=torch.long, device=device)
         for t in range(seq_len - 1):
-            logits = eng.prefix_logits(seq) if txf else eng.decode_step(d, seq[:, -1].contiguous(), t)
+            logits = eng.prefix_logits(seq) if rerun else eng.decode_step(d, seq[:, -1].contiguous(), t)
             if not sample:
                 nxt = logits.argmax(dim=-1, keepdim=True)
             else:
