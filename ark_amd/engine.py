@@ -2128,9 +2128,10 @@ class Engine:
         return d
 
     @torch.no_grad()
-    def decode_begin(self, B, z=None):
+    def decode_begin(self, B, z=None, block=None):
         """start an incremental decode of B sequences: h0 = tanh(z_proj(z)) for every layer (SAIL, reference
-        models.py:139-140) or zeros (ARK, models.py:340-345).  Exact-fp32 register-staged kernels."""
+        models.py:139-140) or zeros (ARK, models.py:340-345).  Exact-fp32 register-staged kernels.  `block` (rows per
+        beam) is read by TxfEngine's prefix state alone."""
         self.dp_flush()
         d = self._decode_ws(B)
         st = L.cur_stream()
@@ -2174,13 +2175,23 @@ class Engine:
         return d["logits"][:, :V]
 
     @torch.no_grad()
+    def decode_reorder(self, d, j, t):
+        """beam search: block i of the beam axis continues beam j[i].  Gathers, block-wise, the half of every layer's state
+        that decode_step(d, ., t) just wrote"""
+        beam = j.numel()
+        for y in d["Y"]:
+            half = y.view(2, beam, -1, self.D)[(t + 1) % 2]
+            half.copy_(half.index_select(0, j))
+
+    # ------------------------------------------------------------------ generation: ONE pair of loops for every engine, over
+    # the state protocol decode_begin(B, z) -> d, decode_step(d, cur, t) -> logits [B, V], decode_reorder(d, j, t)
+    @torch.no_grad()
     def greedy_decode(self, z, max_len=None, bos=1, eos=2):
-        """token sequences of SAIL.decode_latent(z, beam=1) (reference models.py:282-300): the decoder is a causal
-        GRU, so instead of re-running the whole prefix we advance one step per token.  Exact-fp32 kernels on
-        persistent buffers; every step is queued without a host round trip and the reference's stopping rule
-        (first position at which EVERY row's token is EOS) is applied once at the end -- positions up to there do
-        not depend on later ones, so the result is the reference's, token for token."""
-        assert self.mt == "SAIL"
+        """token sequences of SAIL.decode_latent(z, beam=1) (reference models.py:282-300): instead of re-running the
+        whole prefix the decoder advances one step per token.  Every step is queued without a host round trip and the
+        reference's stopping rule (first position at which EVERY row's token is EOS) is applied once at the end --
+        positions up to there do not depend on later ones, so the result is the reference's, token for token."""
+        assert self.mt in ("SAIL", "t-SAIL")
         B = z.shape[0]
         Lmax = (self.seq_len - 1) if max_len is None else max_len
         d = self.decode_begin(B, z)
@@ -2188,10 +2199,9 @@ class Engine:
         toks.fill_(eos)
         toks[:, 0] = bos
         st = L.cur_stream()
-        ldl = d["logits"].shape[1]
         for t in range(Lmax):
-            self.decode_step(d, toks[:, t].contiguous() if t == 0 else d["nxt"], t)
-            _call("ark_argmax_rows", L.ptr(d["logits"]), L.i64(ldl), L.ptr(d["nxt"]), L.i32(B), L.i32(self.V), st)
+            logits = self.decode_step(d, toks[:, t].contiguous() if t == 0 else d["nxt"], t)
+            _call("ark_argmax_rows", L.ptr(logits), L.i64(logits.stride(0)), L.ptr(d["nxt"]), L.i32(B), L.i32(self.V), st)
             toks[:, t + 1] = d["nxt"]
         done = (toks[:, 1:Lmax + 1] == eos).all(dim=0)          # ONE synchronisation, after the last step
         hit = torch.nonzero(done)
@@ -2202,15 +2212,14 @@ class Engine:
     def beam_decode(self, z, beam, max_len=None, bos=1, eos=2):
         """token sequences of SAIL.decode_latent(z, beam > 1) (reference models.py:282-300: a batch-shared beam,
         candidates ranked by the batch-MEAN log-probability, stable descending sort).  The reference re-runs the decoder
-        on every beam's whole prefix per generated token; here every beam keeps its GRU state (beam x B rows of one
-        incremental decode), advances ONE token per step, and the surviving beams' states are gathered block-wise.
-        Exact-fp32 kernels.  One host synchronisation per step for the reference's stopping rule."""
-        assert self.mt == "SAIL" and beam >= 1
+        on every beam's whole prefix per generated token; here every beam keeps its state (beam x B rows of one
+        incremental decode), advances ONE token per step, and decode_reorder gathers the surviving beams' states
+        block-wise.  One host synchronisation per step for the reference's stopping rule."""
+        assert self.mt in ("SAIL", "t-SAIL") and beam >= 1
         B = z.shape[0]
         Lmax = (self.seq_len - 1) if max_len is None else max_len
-        Bt = beam * B
         zr = z.to(self.device, dtype=torch.float32).repeat(beam, 1)
-        d = self.decode_begin(Bt, zr)
+        d = self.decode_begin(beam * B, zr, block=B)
         dev = self.device
         toks = torch.full((beam, B, Lmax + 1), eos, dtype=torch.int64, device=dev)
         toks[:, :, 0] = bos
@@ -2228,13 +2237,9 @@ class Engine:
             scores = scores[j] + top_lp[j, :, k]
             toks = toks[j]
             toks[:, :, t + 1] = new_tok
-            half = (t + 1) % 2                                            # decode_step left the new state in this half
-            for l in range(self.n):
-                y = d["Y"][l].view(2, beam, B, self.D)
-                y[half].copy_(y[half].index_select(0, j))
+            self.decode_reorder(d, j, t)
             active = beam
             length = t + 2
             if bool((new_tok == eos).all()):                                # every beam's last token is EOS
                 break
         return toks[0, :, :length].clone()
-

@@ -964,10 +964,14 @@ class TxfEngine(Engine):
         return w16
 
     @torch.no_grad()
-    def decode_begin(self, B, z=None):
+    def decode_begin(self, B, z=None, block=None):
         """start an incremental decode of B sequences (mirrors Engine.decode_begin).  t-SAIL: mem = z_proj(z), and per layer
         the cross-attention term ca_l = out_proj_l(v_proj_l(mem)) ONCE: the memory is the same row at every position, so in eval
-        mode the context is the value row itself, whatever the query and the position are (_cross_attn_fwd)."""
+        mode the context is the value row itself, whatever the query and the position are (_cross_attn_fwd).
+        `ark_txf_kv_cache: 0` (read here, per generation): the prefix state, stepped `block` rows (one beam) at a time;
+        decode_step and decode_reorder dispatch on the kind of state."""
+        if not self.kv_cache:
+            return self._prefix_begin(B, z, block)
         self.prec = self.prec_fwd
         d = self._decode_ws(B)
         d["w16"] = self._decode_w16()
@@ -995,6 +999,8 @@ class TxfEngine(Engine):
         B, D, n, V = d["B"], self.D, self.n, self.V
         if cur.shape[0] != B or not 0 <= t < self.seq_len:
             raise L.ArkError(f"decode_step: {cur.shape[0]} tokens at position {t} for a state of {B} rows, {self.seq_len} positions")
+        if "kv" not in d:
+            return self._prefix_step(d, cur, t)
         self.prec = self.prec_fwd
         KM, p, w16 = L.LAY_KMAJ, self.p, d["w16"]
         st = L.cur_stream()
@@ -1034,109 +1040,27 @@ class TxfEngine(Engine):
         beam = j.numel()
         if j.tolist() == list(range(beam)):
             return
+        if "kv" not in d:   # the prefix state: its token rows
+            seq = d["seq"].view(beam, -1, self.seq_len)
+            seq.copy_(seq.index_select(0, j))
+            return
         for kv in d["kv"]:
             blk = kv.view(self.seq_len, beam, d["B"] // beam, 2 * self.D)[:t + 1]
             blk.copy_(blk.index_select(1, j))
 
-    @torch.no_grad()
-    def greedy_decode(self, z, max_len=None, bos=1, eos=2):
-        """token sequences of SAIL.decode_latent(z, beam=1) for t-SAIL (reference models.py:282-300): argmax of the next
-        position, stop once every row ends in EOS.  One token per step over the K/V caches; as Engine.greedy_decode, every step
-        is queued without a host round trip and the stopping rule (first position at which EVERY row's token is EOS) is applied
-        once at the end -- positions up to there do not depend on later ones.  `ark_txf_kv_cache: 0`: the prefix re-run."""
-        assert self.vae
-        if not self.kv_cache:
-            return self._greedy_decode_prefix(z, max_len, bos, eos)
-        B = z.shape[0]
-        Lmax = (self.seq_len - 1) if max_len is None else max_len
-        d = self.decode_begin(B, z)
-        toks = d["toks"]
-        toks.fill_(eos)
-        toks[:, 0] = bos
-        st = L.cur_stream()
-        for t in range(Lmax):
-            self.decode_step(d, toks[:, t].contiguous() if t == 0 else d["nxt"], t)
-            _call("ark_argmax_rows", L.ptr(d["logits"]), L.i64(self.ldl), L.ptr(d["nxt"]), L.i32(B), L.i32(self.V), st)
-            toks[:, t + 1] = d["nxt"]
-        done = (toks[:, 1:Lmax + 1] == eos).all(dim=0)          # ONE synchronisation, after the last step
-        hit = torch.nonzero(done)
-        stop = int(hit[0]) + 1 if hit.numel() else Lmax
-        return toks[:, :stop + 1].clone()
-
-    @torch.no_grad()
-    def beam_decode(self, z, beam, max_len=None, bos=1, eos=2):
-        """the reference's batch-shared beam (models.py:282-300): candidates ranked by the batch-MEAN accumulated
-        log-probability (stable descending sort), stop when every kept beam ends in EOS everywhere.  beam x B rows of ONE
-        incremental decode, with the ranking and stopping logic of Engine.beam_decode; the surviving beams' cache blocks are
-        gathered by decode_reorder.  `ark_txf_kv_cache: 0`: the prefix re-run."""
-        assert self.vae and beam >= 1
-        if not self.kv_cache:
-            return self._beam_decode_prefix(z, beam, max_len, bos, eos)
-        B = z.shape[0]
-        Lmax = (self.seq_len - 1) if max_len is None else max_len
-        zr = z.to(self.device, dtype=torch.float32).repeat(beam, 1)
-        d = self.decode_begin(beam * B, zr)
+    # ------------------------------------------------------------------ `ark_txf_kv_cache: 0`: the prefix state (the checker)
+    def _prefix_begin(self, B, z, block):
+        """a decode state that re-runs the whole prefix per token, as the reference does: the tokens so far (`seq`), z for
+        t-SAIL, and the buffers the generation loops use.  prefix_logits runs on `block` rows (one beam) at a time: its
+        workspace and its [block * L, V] logits keep the size of a single beam's."""
         dev = self.device
-        toks = torch.full((beam, B, Lmax + 1), eos, dtype=torch.int64, device=dev)
-        toks[:, :, 0] = bos
-        scores = torch.zeros(beam, B, device=dev)
-        active = 1          # distinct beams so far (all blocks start as copies of the single BOS beam)
-        length = 1
-        for t in range(Lmax):
-            logits = self.decode_step(d, toks[:, :, t].reshape(-1).contiguous(), t)
-            logp = torch.log_softmax(logits.float(), dim=-1).view(beam, B, -1)
-            top_lp, ids = logp.topk(beam, dim=-1)                         # [beam, B, beam]
-            cand = (scores[:, :, None] + top_lp)[:active]                 # candidate (j, k) = beam j extended by its k-th token
-            order = torch.sort(cand.mean(dim=1).reshape(-1), descending=True, stable=True).indices[:beam]
-            j, k = order // beam, order % beam
-            new_tok = ids[j, :, k]                                        # [beam, B]
-            scores = scores[j] + top_lp[j, :, k]
-            toks = toks[j]
-            toks[:, :, t + 1] = new_tok
-            self.decode_reorder(d, j, t)
-            active = beam
-            length = t + 2
-            if bool((new_tok == eos).all()):                                # every beam's last token is EOS
-                break
-        return toks[0, :, :length].clone()
+        i = lambda *sh: torch.zeros(*sh, dtype=torch.int64, device=dev)
+        return {"B": B, "block": block or B, "seq": i(B, self.seq_len), "toks": i(B, self.seq_len), "nxt": i(B),
+                "z": None if z is None else z.to(dev, dtype=torch.float32), "logits": torch.zeros(B, self.ldl, device=dev)}
 
-    @torch.no_grad()
-    def _greedy_decode_prefix(self, z, max_len=None, bos=1, eos=2):
-        """token sequences of SAIL.decode_latent(z, beam=1) for t-SAIL (reference models.py:282-300): prefix re-run,
-        argmax of the last position, stop once every row ends in EOS"""
-        assert self.vae
-        B = z.shape[0]
-        Lmax = (self.seq_len - 1) if max_len is None else max_len
-        z = z.to(self.device, dtype=torch.float32)
-        s = torch.full((B, 1), bos, dtype=torch.int64, device=self.device)
-        nxt = torch.empty(B, dtype=torch.int64, device=self.device)
-        for _ in range(Lmax):
-            logits = self.prefix_logits(s, z)
-            _call("ark_argmax_rows", L.ptr(logits), L.i64(self.ldl), L.ptr(nxt), L.i32(B), L.i32(self.V), L.cur_stream())
-            s = torch.cat([s, nxt[:, None]], 1)
-            if bool((s[:, -1] == eos).all()):
-                break
-        return s
-
-    @torch.no_grad()
-    def _beam_decode_prefix(self, z, beam, max_len=None, bos=1, eos=2):
-        """the reference's batch-shared beam (models.py:282-300) on prefix re-runs: candidates ranked by the batch-MEAN
-        accumulated log-probability (stable descending sort), stop when every kept beam ends in EOS everywhere"""
-        assert self.vae and beam >= 1
-        B = z.shape[0]
-        Lmax = (self.seq_len - 1) if max_len is None else max_len
-        z = z.to(self.device, dtype=torch.float32)
-        beams = [(torch.full((B, 1), bos, dtype=torch.int64, device=self.device), torch.zeros(B, device=self.device))]
-        for _ in range(Lmax):
-            cand = []
-            for s, lp in beams:
-                logp = torch.log_softmax(self.prefix_logits(s, z).float(), dim=-1)
-                top_lp, ids = logp.topk(beam, dim=-1)
-                for k in range(beam):
-                    cand.append((torch.cat([s, ids[:, k:k + 1]], 1), lp + top_lp[:, k]))
-            means = torch.stack([c[1].mean() for c in cand])
-            order = torch.sort(means, descending=True, stable=True).indices[:beam].tolist()
-            beams = [cand[i] for i in order]
-            if all(bool((s[:, -1] == eos).all()) for s, _ in beams):
-                break
-        return beams[0][0]
+    def _prefix_step(self, d, cur, t):
+        d["seq"][:, t] = cur
+        for r in range(0, d["B"], d["block"]):
+            rows = slice(r, r + d["block"])
+            d["logits"][rows, :self.V] = self.prefix_logits(d["seq"][rows, :t + 1], None if d["z"] is None else d["z"][rows])
+        return d["logits"][:, :self.V]

@@ -239,14 +239,11 @@ class SAIL(_EngineModel):
     @torch.no_grad()
     def beam_generate(self, seq_len, special_tokens, seq_to_triples, z, ent_base, rel_base, beam=4):
         eng = self.engine()
-        if beam == 1:
-            # beam 1 == greedy argmax per row; the decoder (causal GRU, or the Transformer over its K/V caches) is
-            # advanced one token per step on the device instead of re-running the whole prefix
-            best = eng.greedy_decode(z, max_len=seq_len - 1, bos=special_tokens["BOS"], eos=special_tokens["EOS"]).cpu()
-            return [seq_to_triples(row, special_tokens, ent_base, rel_base) for row in best]
-        # beam > 1: the reference's batch-shared beam (candidates ranked by the batch-MEAN log-prob); every beam keeps its
-        # GRU state on the device and advances one token per step (Engine.beam_decode)
-        best = eng.beam_decode(z, beam, max_len=seq_len - 1, bos=special_tokens["BOS"], eos=special_tokens["EOS"]).cpu()
+        # beam 1 == greedy argmax per row; beam > 1: the reference's batch-shared beam (candidates ranked by the batch-MEAN
+        # log-prob).  Either way the decoder keeps its state on the device (GRU states, or the Transformer's K/V caches) and
+        # advances one token per step instead of re-running the whole prefix (Engine.greedy_decode / beam_decode)
+        kw = dict(max_len=seq_len - 1, bos=special_tokens["BOS"], eos=special_tokens["EOS"])
+        best = (eng.greedy_decode(z, **kw) if beam == 1 else eng.beam_decode(z, beam, **kw)).cpu()
         return [seq_to_triples(row, special_tokens, ent_base, rel_base) for row in best]
 
     @torch.no_grad()
@@ -363,7 +360,7 @@ class ARK(_EngineModel):
         """autoregressive generation with the reference's sampling rules (models.py:407-471): greedy, or
         temperature / top-k / nucleus sampling.  The decoder advances ONE token per step on the engine (the causal GRU:
         Engine.decode_step, exact-fp32 kernels; t-ARK: TxfEngine.decode_step over K/V caches) instead of re-running the whole
-        prefix.
+        prefix; with `ark_txf_kv_cache: 0` t-ARK's state re-runs the prefix inside decode_step, as the reference does.
 
         Draws: with a nucleus the reference draws in SORTED space, one torch.multinomial per row, and maps the drawn
         position back through the sort; otherwise one batched multinomial over the dense distribution.  By default the
@@ -375,13 +372,10 @@ class ARK(_EngineModel):
         B = batch_size
         bos, eos = special_tokens["BOS"], special_tokens["EOS"]
         eng = self.engine()
-        # t-ARK advances one token per step too, over per-layer K/V caches (TxfEngine.decode_step); `ark_txf_kv_cache: 0`
-        # re-runs the whole prefix per token, as the reference does
-        rerun = self.config["model_type"] == "t-ARK" and not eng.kv_cache
-        d = None if rerun else eng.decode_begin(B)
+        d = eng.decode_begin(B)
         seq = torch.full((B, 1), bos, dtype=torch.long, device=device)
         for t in range(seq_len - 1):
-            logits = eng.prefix_logits(seq) if rerun else eng.decode_step(d, seq[:, -1].contiguous(), t)
+            logits = eng.decode_step(d, seq[:, -1].contiguous(), t)
             if not sample:
                 nxt = logits.argmax(dim=-1, keepdim=True)
             else:

@@ -48,21 +48,15 @@ def run_leg(name, precision, batch, kernel_time):
     st, seq_len = cfg["special_tokens"], cfg["seq_len"]
     z = torch.randn(batch, cfg["d_latent"], generator=torch.Generator().manual_seed(1)).cuda()
     steps = {"n": 0}
-    for fn in ("decode_step", "prefix_logits"):
-        def counted(*a, _f=getattr(eng, fn), **k):
-            steps["n"] += 1
-            return _f(*a, **k)
-        setattr(eng, fn, counted)
+    def counted(*a, _f=eng.decode_step, **k):
+        steps["n"] += 1
+        return _f(*a, **k)
+    eng.decode_step = counted
 
     def generate(length):
         if mt == "t-ARK":
             return model.generate(length, st, batch_size=batch)
         return model.decode_latent(z, length, st, seq_to_triples, cfg["ENT_BASE"], cfg["REL_BASE"], beam=beam)
-
-    def tokens(on):
-        """generated positions of the last generation, from the per-step call count (the prefix beam runs every kept beam)"""
-        n = steps["n"]
-        return n if (on or beam == 1) else 1 + (n - 1) // beam
 
     out = {"model": mt, "workload": wl, "beam": beam, "batch": batch, "seq_len": seq_len, "precision": precision}
     reps = 5 if seq_len <= 64 else 1
@@ -79,7 +73,7 @@ def run_leg(name, precision, batch, kernel_time):
             generate(seq_len)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            ntok = tokens(on)
+            ntok = steps["n"]   # generated positions = decode_step calls (the prefix state re-runs its beams inside one)
             launches = (E._calls[0] - c0) / ntok
             ms.append(dt * 1e3 / ntok)
         res = {"ms_per_token": statistics.median(ms), "tokens": ntok, "library_launches_per_token": round(launches, 2), "generations_timed": reps,
@@ -97,9 +91,9 @@ def run_leg(name, precision, batch, kernel_time):
                     if ev.device_type == DeviceType.CUDA:   # device-side events: their own duration
                         us += float(ev.device_time_total)
                         nk += 1
-                res["kernel_events_per_token"] = round(nk / tokens(on), 2)
-                if nk >= launches * tokens(on):
-                    res["kernel_ms_per_token"] = us / 1e3 / tokens(on)
+                res["kernel_events_per_token"] = round(nk / steps["n"], 2)
+                if nk >= launches * steps["n"]:
+                    res["kernel_ms_per_token"] = us / 1e3 / steps["n"]
                 else:   # (fewer device events than library launches: the profiler's buffer dropped some -- no figure)
                     res["kernel_time_error"] = "the profiler kept fewer kernel events than the library launched"
             except Exception as e:   # (a figure that could not be taken is reported as missing, never estimated)
