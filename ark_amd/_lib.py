@@ -71,6 +71,10 @@ def u64(x):
     return ctypes.c_uint64(int(x) & 0xFFFFFFFFFFFFFFFF)
 
 
+def u32(x):
+    return ctypes.c_uint32(int(x) & 0xFFFFFFFF)
+
+
 DIAG_MAX_ROLES = 4
 WGRAD_MAX_GROUP = 12
 ADAM_MAX_JOBS = 48

@@ -72,6 +72,23 @@ def _call(name, *args):
         L.check(L.lib().ark_stamp(L.ptr(_stamps["buf"]), L.i32(len(_stamps["log"]) - 1), st), "ark_stamp")
 
 
+SAMPLE_MAX_V = 65536   # ark_sample_rows keeps a row's weights on one CU (csrc/sample.hip)
+
+
+def sample_rows(logits, out, V=None, sample=True, temperature=1.0, top_p=0.0, top_k=0, seed=0, draw=0, u_in=None, u_out=None,
+                forced=-1, out2=None):
+    """ark_sample_rows on the current stream: one token per row of `logits` [rows, >= V] (fp32, unit column stride) into the
+    int64 view `out` [rows] (any row stride) and, when given, the contiguous `out2` [rows]"""
+    rows = logits.shape[0]
+    V = logits.shape[1] if V is None else V
+    if V > SAMPLE_MAX_V:
+        raise L.ArkError(f"the fused sampler holds vocabularies up to {SAMPLE_MAX_V} (this one: {V}): use sampler='torch'")
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and out.dtype == torch.int64 and out.shape[0] == rows
+    _call("ark_sample_rows", L.ptr(logits), L.i64(logits.stride(0)), L.i32(rows), L.i32(V), L.i32(1 if sample else 0),
+          L.f32(temperature), L.f32(top_p), L.i32(top_k), L.u64(seed), L.u32(draw), L.ptr(u_in), L.ptr(u_out), L.i64(forced),
+          L.ptr(out), L.i64(out.stride(0) if rows > 1 else 1), L.ptr(out2), L.cur_stream())
+
+
 class ParamLayout:
     """name -> (offset, shape) inside the flat buffers.  Blocks start on 16-byte boundaries."""
 
@@ -2206,6 +2223,42 @@ class Engine:
         done = (toks[:, 1:Lmax + 1] == eos).all(dim=0)          # ONE synchronisation, after the last step
         hit = torch.nonzero(done)
         stop = int(hit[0]) + 1 if hit.numel() else Lmax
+        return toks[:, :stop + 1].clone()
+
+    @torch.no_grad()
+    def sample_decode(self, B, z=None, max_len=None, bos=1, eos=2, sample=True, temperature=1.0, top_p=0.0, top_k=0, seed=0,
+                      forced=None, check_every=16):
+        """B token sequences drawn with the reference's sampling rules (models.py:407-471; greedy with sample=False) for any of
+        the four models (`z` [B, Z] for SAIL / t-SAIL), every next token chosen on the device by ONE ark_sample_rows launch
+        that writes it into column t + 1 of the persistent `toks` buffer and into `nxt`, the next step's input.  The draw
+        counter is the column, so a sequence depends on (seed, row, column) only.  `forced` = {column: token id}: those
+        columns hold that token in every row (conditioned generation, the reference's force_token).  The reference's
+        stopping rule -- the first column at which EVERY row's token is EOS -- is applied once per `check_every` columns
+        (one reduction over those columns, one synchronisation): columns up to the stop do not depend on later ones, so the
+        result, truncated there, is the one of stopping at that column exactly, whatever check_every is."""
+        Lmax = (self.seq_len - 1) if max_len is None else int(max_len)
+        if not 0 < Lmax <= self.seq_len - 1:
+            raise L.ArkError(f"sample_decode: max_len {Lmax} outside 1 .. seq_len - 1 = {self.seq_len - 1}")
+        forced = {int(k): int(v) for k, v in (forced or {}).items()}
+        if any(not 0 <= v < self.V for v in forced.values()):
+            raise L.ArkError(f"sample_decode: forced token outside the vocabulary of {self.V}")
+        check_every = max(1, int(check_every))
+        d = self.decode_begin(B, z)
+        toks = d["toks"]
+        toks.fill_(eos)
+        toks[:, 0] = bos
+        first = toks[:, 0].contiguous()
+        stop, c0 = Lmax, 1          # columns c0 .. are not yet checked
+        for t in range(Lmax):
+            logits = self.decode_step(d, first if t == 0 else d["nxt"], t)
+            sample_rows(logits, toks[:, t + 1], V=self.V, sample=sample, temperature=temperature, top_p=top_p, top_k=top_k,
+                        seed=seed, draw=t + 1, forced=forced.get(t + 1, -1), out2=d["nxt"])
+            if (t + 1) % check_every == 0 or t == Lmax - 1:
+                done = (toks[:, c0:t + 2] == eos).all(dim=0).cpu().numpy()
+                if done.any():
+                    stop = c0 + int(done.argmax())
+                    break
+                c0 = t + 2
         return toks[:, :stop + 1].clone()
 
     @torch.no_grad()

@@ -428,6 +428,17 @@ int ark_loss_finalize(const float* row_loss, int n_rows, const float* kl, const 
 int ark_loss_finalize_rows(const float* row_loss, int n_rows, const float* kl_rows, int n_kl, float kl_scale,
                            const float* hyper, float* out4, void* stream);
 int ark_argmax_rows(const float* x, int64_t ld, int64_t* out, int rows, int V, void* stream);
+/* Fused next-token sampler (csrc/sample.hip), one launch for all rows of logits[rows, V] (fp32, leading dimension ld >= V,
+ * V <= 65536): weights w = exp((l - max l) / temperature) (temperature 0 or 1: none), top_k largest kept when 0 < top_k < V,
+ * then with 0 < top_p < 1 the prefix of the stable descending order (equal weights: lower index first) up to and including
+ * the first position whose cumulative mass exceeds top_p * (kept mass), then the first kept position whose cumulative mass
+ * exceeds u * (kept mass), clamped to the last kept one.  u in [0, 1) has 24 bits: u_in[row] when u_in is given, otherwise
+ * the counter hash of (seed, draw, row), written to u_out[row] when u_out is given.  sample == 0: the row's argmax, as
+ * ark_argmax_rows.  forced_tok >= 0: every row returns forced_tok.  The token goes to out[row * out_stride] and, when out2
+ * is given, to out2[row].  No sort, no float atomics: the same inputs give the same tokens on every run. */
+int ark_sample_rows(const float* logits, int64_t ld, int rows, int V, int sample, float temperature, float top_p, int top_k,
+                    uint64_t seed, uint32_t draw, const float* u_in, float* u_out, int64_t forced_tok, int64_t* out,
+                    int64_t out_stride, int64_t* out2, void* stream);
 
 /* ---- Transformer variant t-ARK (reference: DecoderOnlyTransformer, kgvae/model/models.py:349-366 = stock
  *      nn.TransformerEncoderLayer stack: post-norm, ReLU feed-forward, causal mask).  Rows are time-major (t, b);

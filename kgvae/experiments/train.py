@@ -418,7 +418,7 @@ def main(argv=None):
                 while sum(c.size(0) for c in chunks) < target_n:
                     chunks.append(model.generate(seq_len, special_tokens, device=device, batch_size=50, beam=1, sample=True,
                                                  temperature=config.get("temperature", 1.0), top_p=config.get("top_p", 0.9),
-                                                 top_k=config.get("top_k", 0)).cpu())
+                                                 top_k=config.get("top_k", 0), sampler=config.get("ark_sampler", "torch")).cpu())
                 rows = torch.cat(chunks, 0)[:target_n]
                 graphs = [seq_to_triples(r, special_tokens, ENT_BASE, REL_BASE) for r in rows]
             labels = ints_to_labels(graphs, i2e, i2r)

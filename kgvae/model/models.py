@@ -29,6 +29,17 @@ from ark_amd._lib import ArkError
 from kgvae.model.utils import canonical_graph_string
 
 
+def _draw_seed(seed):
+    """the fused sampler's seed: as given, or one 63-bit integer from torch's default CPU generator"""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)) if seed is None else int(seed)
+
+
+def _pad_eos(toks, seq_len, eos):
+    if toks.size(1) < seq_len:
+        toks = torch.cat([toks, torch.full((toks.size(0), seq_len - toks.size(1)), eos, dtype=toks.dtype, device=toks.device)], 1)
+    return toks[:, :seq_len]
+
+
 class _Holder(nn.Module):
     """named container of stock modules (keeps the reference's state-dict key layout)"""
 
@@ -247,6 +258,21 @@ class SAIL(_EngineModel):
         return [seq_to_triples(row, special_tokens, ent_base, rel_base) for row in best]
 
     @torch.no_grad()
+    def sample_latent(self, z, seq_len, special_tokens, sample=False, temperature=1.0, top_p=0.0, top_k=0, seed=None,
+                      forced=None):
+        """token sequences [B, seq_len] decoded from the latents z one token at a time, greedy or with ARK.generate's
+        sampling rules, on the engine's fused sampler (Engine.sample_decode); `forced` = {position: token id} fixes those
+        positions in every row.  The autoregressive half of the reference's conditional_generate
+        (kgvae/experiments/conditioned.py); `seed` as in ARK.generate."""
+        self.eval()
+        eng = self.engine()
+        z = z.to(next(self.parameters()).device, dtype=torch.float32)
+        bos, eos = special_tokens["BOS"], special_tokens["EOS"]
+        toks = eng.sample_decode(z.shape[0], z, max_len=seq_len - 1, bos=bos, eos=eos, sample=sample, temperature=temperature,
+                                 top_p=top_p, top_k=top_k, seed=_draw_seed(seed), forced=forced)
+        return _pad_eos(toks, seq_len, eos)
+
+    @torch.no_grad()
     def count_unique_graphs(self, latent_dim, decode_latent_fn, num_samples=1000, beam=1):
         self.eval()
         zs = torch.randn((num_samples, latent_dim), device=next(self.parameters()).device)
@@ -356,7 +382,7 @@ class ARK(_EngineModel):
 
     @torch.no_grad()
     def generate(self, seq_len, special_tokens, device=None, batch_size=1, beam=1, sample=False, temperature=1.0,
-                 top_p=0.0, top_k=0, host_draws=False):
+                 top_p=0.0, top_k=0, host_draws=False, sampler="torch", seed=None, forced=None):
         """autoregressive generation with the reference's sampling rules (models.py:407-471): greedy, or
         temperature / top-k / nucleus sampling.  The decoder advances ONE token per step on the engine (the causal GRU:
         Engine.decode_step, exact-fp32 kernels; t-ARK: TxfEngine.decode_step over K/V caches) instead of re-running the whole
@@ -367,11 +393,27 @@ class ARK(_EngineModel):
         draws are made on the device (one batched multinomial per step, in sorted space under a nucleus: the same
         distribution, the device generator's stream).  `host_draws=True` copies each step's logits to the host and makes
         the reference's draws there, call for call, from torch's global CPU generator: under the same torch.manual_seed
-        the sampled tokens are then the reference's CPU path's, token for token (tests/golden/ark_sampling.npz)."""
+        the sampled tokens are then the reference's CPU path's, token for token (tests/golden/ark_sampling.npz).
+
+        `sampler="fused"`: the same distribution drawn by the engine's fused sampler (Engine.sample_decode: one
+        ark_sample_rows launch per token, no sort, the stopping rule checked every 16 tokens).  Its draws are a function of
+        (`seed`, row, position): the same seed reproduces a generation; `seed=None` takes one 63-bit integer from torch's
+        default CPU generator per call, so torch.manual_seed reproduces a run and successive calls differ.
+        `forced` = {position: token id} fixes those positions in every row (conditioned generation)."""
         device = device or next(self.parameters()).device
         B = batch_size
         bos, eos = special_tokens["BOS"], special_tokens["EOS"]
         eng = self.engine()
+        if sampler == "fused":
+            if host_draws:
+                raise ValueError("host_draws=True makes the reference's draws on the host: it needs sampler='torch'")
+            toks = eng.sample_decode(B, None, max_len=seq_len - 1, bos=bos, eos=eos, sample=sample, temperature=temperature,
+                                     top_p=top_p, top_k=top_k, seed=_draw_seed(seed), forced=forced)
+            return _pad_eos(toks, seq_len, eos)
+        if sampler != "torch":
+            raise ValueError(f"sampler {sampler!r}: 'torch' or 'fused'")
+        if forced is not None or seed is not None:
+            raise ValueError("seed= and forced= belong to sampler='fused'")
         d = eng.decode_begin(B)
         seq = torch.full((B, 1), bos, dtype=torch.long, device=device)
         for t in range(seq_len - 1):
