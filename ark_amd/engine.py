@@ -89,6 +89,35 @@ def sample_rows(logits, out, V=None, sample=True, temperature=1.0, top_p=0.0, to
           L.ptr(out), L.i64(out.stride(0) if rows > 1 else 1), L.ptr(out2), L.cur_stream())
 
 
+BEAM_MAX = 8           # ark_beam_step_rows keeps a latent's beam x beam candidates in one wave (csrc/beam.hip)
+
+
+def beam_step_rows(logits, scores, done, lens, tok_out, nxt, parent_out, t, active, eos, V=None):
+    """ark_beam_step_rows on the current stream: one beam step for every latent.  `logits` [beam * B, >= V] (fp32, unit column
+    stride, row j * B + b = beam j of latent b), `scores` [beam, B] fp32 (in place), `done` / `lens` [B] int32, `tok_out` and
+    `nxt` [beam, B] / [beam * B] int64, `parent_out` [beam, B] int32, all contiguous"""
+    beam, B = scores.shape
+    V = logits.shape[1] if V is None else V
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == beam * B
+    assert scores.dtype == torch.float32 and done.dtype == torch.int32 and lens.dtype == torch.int32
+    assert tok_out.dtype == torch.int64 and nxt.dtype == torch.int64 and parent_out.dtype == torch.int32
+    assert done.numel() == B and lens.numel() == B
+    for a in (scores, tok_out, nxt, parent_out):
+        assert a.is_contiguous() and a.numel() == beam * B
+    _call("ark_beam_step_rows", L.ptr(logits), L.i64(logits.stride(0)), L.i32(B), L.i32(V), L.i32(beam), L.i32(active),
+          L.i32(eos), L.i32(t), L.ptr(scores), L.ptr(done), L.ptr(lens), L.ptr(tok_out), L.ptr(nxt), L.ptr(parent_out),
+          L.cur_stream())
+
+
+def beam_gather_rows(x, parent):
+    """ark_beam_gather_rows on the current stream: x[o, i, b, :] = x[o, parent[i, b], b, :] in place; `x` [outer, beam, B, width]
+    fp32 contiguous, `parent` [beam, B] int32 contiguous"""
+    outer, beam, B, width = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    assert parent.dtype == torch.int32 and parent.is_contiguous() and tuple(parent.shape) == (beam, B)
+    _call("ark_beam_gather_rows", L.ptr(x), L.ptr(parent), L.i64(outer), L.i32(beam), L.i32(B), L.i64(width), L.cur_stream())
+
+
 class ParamLayout:
     """name -> (offset, shape) inside the flat buffers.  Blocks start on 16-byte boundaries."""
 
@@ -2200,6 +2229,17 @@ class Engine:
             half = y.view(2, beam, -1, self.D)[(t + 1) % 2]
             half.copy_(half.index_select(0, j))
 
+    @torch.no_grad()
+    def decode_reorder_rows(self, d, parent, t):
+        """per-latent beam search: latent b of block i continues from block parent[i, b] (`parent` [beam, B] int32 on the
+        device).  One ark_beam_gather_rows per layer, in place, on the half of the layer's state that decode_step(d, ., t)
+        just wrote"""
+        beam, B = parent.shape
+        rows = beam * B
+        for y in d["Y"]:
+            o = ((t + 1) % 2) * rows
+            beam_gather_rows(y[o:o + rows].view(1, beam, B, self.D), parent)
+
     # ------------------------------------------------------------------ generation: ONE pair of loops for every engine, over
     # the state protocol decode_begin(B, z) -> d, decode_step(d, cur, t) -> logits [B, V], decode_reorder(d, j, t)
     @torch.no_grad()
@@ -2296,3 +2336,52 @@ class Engine:
             if bool((new_tok == eos).all()):                                # every beam's last token is EOS
                 break
         return toks[0, :, :length].clone()
+
+    @torch.no_grad()
+    def beam_decode_rows(self, z, beam, max_len=None, bos=1, eos=2, check_every=16):
+        """per-latent beam search: row b of the result is beam_decode(z[b:b+1], beam) -- every latent keeps its OWN `beam`
+        beams, ranks its own candidates and stops on its own (the reference's beam is shared by the batch; only a batch of
+        one latent gives a latent its own beam, models.py:282-300).  -> (toks [B, Lmax + 1] padded with EOS past each row's
+        length, lengths [B]); a latent that never stops has length Lmax + 1.
+        Per token: decode_step on the beam x B rows, ONE ark_beam_step_rows (log-softmax, per-beam top-`beam`, the candidate
+        ranking, the token / back-pointer / score records and the stopping rule of every latent) and decode_reorder_rows;
+        nothing else, and no host round trip: `done` is read once per `check_every` steps, as sample_decode does.  A latent
+        that is done is left alone by the step kernel, so stopping late changes nothing.  The tokens are read off the
+        back-pointer record at the end, from slot 0 at each latent's own length."""
+        assert self.mt in ("SAIL", "t-SAIL")
+        if not 1 <= beam <= min(BEAM_MAX, self.V) or self.V > SAMPLE_MAX_V:
+            raise L.ArkError(f"beam_decode_rows: beam {beam} outside 1 .. {BEAM_MAX}, or a vocabulary of {self.V} outside "
+                             f"beam .. {SAMPLE_MAX_V}")
+        B = z.shape[0]
+        Lmax = (self.seq_len - 1) if max_len is None else int(max_len)
+        if not 0 < Lmax <= self.seq_len - 1:
+            raise L.ArkError(f"beam_decode_rows: max_len {Lmax} outside 1 .. seq_len - 1 = {self.seq_len - 1}")
+        check_every = max(1, int(check_every))
+        dev = self.device
+        d = self.decode_begin(beam * B, z.to(dev, dtype=torch.float32).repeat(beam, 1), block=B)
+        toks = torch.full((Lmax + 1, beam, B), eos, dtype=torch.int64, device=dev)      # token of slot i at position p
+        toks[0] = bos
+        back = torch.arange(beam, dtype=torch.int32, device=dev).view(1, beam, 1).repeat(Lmax, 1, B)   # parent slot, per step
+        scores = torch.zeros(beam, B, device=dev)
+        done = torch.zeros(B, dtype=torch.int32, device=dev)
+        lens = torch.full((B,), Lmax + 1, dtype=torch.int32, device=dev)
+        first, nxt = toks[0].reshape(-1), d["nxt"]
+        steps = Lmax
+        for t in range(Lmax):
+            logits = self.decode_step(d, first if t == 0 else nxt, t)
+            beam_step_rows(logits, scores, done, lens, toks[t + 1], nxt, back[t], t, 1 if t == 0 else beam, eos, V=self.V)
+            if beam > 1:
+                self.decode_reorder_rows(d, back[t], t)
+            if (t + 1) % check_every == 0 and t + 1 < Lmax and bool(done.all()):
+                steps = t + 1
+                break
+        lens = lens.long()
+        out = torch.full((B, Lmax + 1), eos, dtype=torch.int64, device=dev)
+        out[:, 0] = bos
+        rows = torch.arange(B, device=dev)
+        slot = torch.zeros(B, dtype=torch.int64, device=dev)
+        for p in range(steps, 0, -1):          # positions past a latent's length keep EOS and slot 0
+            live = lens > p
+            out[:, p] = torch.where(live, toks[p, slot, rows], out[:, p])
+            slot = torch.where(live, back[p - 1, slot, rows].long(), slot)
+        return out, lens

@@ -22,7 +22,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib as L
-from .engine import CAPTURE_MODE, Engine, HP, PREC, _call, _rup
+from .engine import CAPTURE_MODE, Engine, HP, PREC, _call, _rup, beam_gather_rows
 from .engine import _calls as _launches   # library calls made so far (TxfEngine._cast: "nothing ran since the previous product")
 
 FF = 2048          # nn.Transformer*Layer default dim_feedforward (the reference never passes another)
@@ -1047,6 +1047,19 @@ class TxfEngine(Engine):
         for kv in d["kv"]:
             blk = kv.view(self.seq_len, beam, d["B"] // beam, 2 * self.D)[:t + 1]
             blk.copy_(blk.index_select(1, j))
+
+    @torch.no_grad()
+    def decode_reorder_rows(self, d, parent, t):
+        """per-latent beam search: latent b of block i continues from block parent[i, b] (`parent` [beam, B] int32 on the
+        device).  One ark_beam_gather_rows per layer over the cache rows of positions 0 .. t, viewed [t + 1, beam, B, 2D]:
+        O(t) per step, as the block-wise reorder.  The prefix state gathers its token rows with torch (it is the checker)"""
+        beam, B = parent.shape
+        if "kv" not in d:
+            seq = d["seq"].view(beam, B, self.seq_len)
+            seq.copy_(torch.take_along_dim(seq, parent.long()[:, :, None], 0))
+            return
+        for kv in d["kv"]:
+            beam_gather_rows(kv.view(self.seq_len, beam, B, 2 * self.D)[:t + 1], parent)
 
     # ------------------------------------------------------------------ `ark_txf_kv_cache: 0`: the prefix state (the checker)
     def _prefix_begin(self, B, z, block):

@@ -439,6 +439,20 @@ int ark_argmax_rows(const float* x, int64_t ld, int64_t* out, int rows, int V, v
 int ark_sample_rows(const float* logits, int64_t ld, int rows, int V, int sample, float temperature, float top_p, int top_k,
                     uint64_t seed, uint32_t draw, const float* u_in, float* u_out, int64_t forced_tok, int64_t* out,
                     int64_t out_stride, int64_t* out2, void* stream);
+/* Per-latent beam search (csrc/beam.hip): ONE beam step for every latent b of a batch in one launch.  logits[beam * B, ld]
+ * (fp32, ld >= V): row j * B + b is beam j of latent b; scores[beam, B] in and out.  active = 1 at the first step (every
+ * block is a copy of the BOS beam), beam afterwards.  Per beam j < active: logp = l - max - log sum exp(l - max) and its
+ * `beam` best entries (descending value, lower index first among equal values, as ark_argmax_rows); candidate j * beam + k
+ * scores scores[j, b] + logp_k; the `beam` best candidates (descending score, lower candidate index first among equal
+ * scores) fill slots i < beam: token -> tok_out[i * B + b] and nxt[i * B + b], parent beam j -> parent_out[i * B + b], score
+ * -> scores[i * B + b].  All kept tokens == eos: done[b] = 1, len[b] = t + 2.  A latent with done[b] != 0 is left alone.
+ * ARK_ERR_SHAPE unless 1 <= beam <= 8 and beam <= V <= 65536.  No logits-sized intermediate, no sort, no float atomics. */
+int ark_beam_step_rows(const float* logits, int64_t ld, int B, int V, int beam, int active, int eos, int t, float* scores,
+                       int* done, int* len, int64_t* tok_out, int64_t* nxt, int* parent_out, void* stream);
+/* x[o, i, b, :] = x[o, parent[i * B + b], b, :] in place on x[outer, beam, B, width] (fp32, contiguous): the state reorder
+ * of a per-latent beam step.  Latents whose parents are the identity are not touched; a parent outside 0 .. beam - 1 counts
+ * as the identity. */
+int ark_beam_gather_rows(float* x, const int* parent, int64_t outer, int beam, int B, int64_t width, void* stream);
 
 /* ---- Transformer variant t-ARK (reference: DecoderOnlyTransformer, kgvae/model/models.py:349-366 = stock
  *      nn.TransformerEncoderLayer stack: post-norm, ReLU feed-forward, causal mask).  Rows are time-major (t, b);

@@ -242,18 +242,25 @@ class SAIL(_EngineModel):
 
     # -- generation (reference models.py:262-315) ------------------------------------------
     @torch.no_grad()
-    def decode_latent(self, z, seq_len, special_tokens, seq_to_triples, ent_base, rel_base, beam=4):
+    def decode_latent(self, z, seq_len, special_tokens, seq_to_triples, ent_base, rel_base, beam=4, per_latent=False):
         self.eval()
         z = z.to(next(self.parameters()).device, dtype=torch.float32)
-        return self.beam_generate(seq_len, special_tokens, seq_to_triples, z, ent_base, rel_base, beam=beam)
+        return self.beam_generate(seq_len, special_tokens, seq_to_triples, z, ent_base, rel_base, beam=beam, per_latent=per_latent)
 
     @torch.no_grad()
-    def beam_generate(self, seq_len, special_tokens, seq_to_triples, z, ent_base, rel_base, beam=4):
+    def beam_generate(self, seq_len, special_tokens, seq_to_triples, z, ent_base, rel_base, beam=4, per_latent=False):
         eng = self.engine()
         # beam 1 == greedy argmax per row; beam > 1: the reference's batch-shared beam (candidates ranked by the batch-MEAN
         # log-prob).  Either way the decoder keeps its state on the device (GRU states, or the Transformer's K/V caches) and
         # advances one token per step instead of re-running the whole prefix (Engine.greedy_decode / beam_decode)
         kw = dict(max_len=seq_len - 1, bos=special_tokens["BOS"], eos=special_tokens["EOS"])
+        if per_latent:
+            # every latent its own beam and its own stop: row i is what decode_latent(z[i:i+1], beam) returns
+            # (Engine.beam_decode_rows).  The row is cut at its length: the parser stops on EOS or at the end of what it is
+            # given, so an EOS-padded row could end in a spurious (h, r, EOS) triple
+            toks, lens = eng.beam_decode_rows(z, beam, **kw)
+            toks, lens = toks.cpu(), lens.cpu().tolist()
+            return [seq_to_triples(row[:n], special_tokens, ent_base, rel_base) for row, n in zip(toks, lens)]
         best = (eng.greedy_decode(z, **kw) if beam == 1 else eng.beam_decode(z, beam, **kw)).cpu()
         return [seq_to_triples(row, special_tokens, ent_base, rel_base) for row in best]
 
