@@ -453,6 +453,24 @@ int ark_beam_step_rows(const float* logits, int64_t ld, int B, int V, int beam, 
  * of a per-latent beam step.  Latents whose parents are the identity are not touched; a parent outside 0 .. beam - 1 counts
  * as the identity. */
 int ark_beam_gather_rows(float* x, const int* parent, int64_t outer, int beam, int B, int64_t width, void* stream);
+/* Canonical graphs (csrc/graphkey.hip).  toks[B, ld] int64, row_len <= ld tokens per row, lens[B] int64 nullable (row b is cut
+ * at min(max(lens[b], 0), row_len)).  Parsed as kgvae.model.utils.seq_to_triples: position 0 skipped, slot s = positions
+ * 1 + 3s .. 3 + 3s, the list ends in front of the first slot whose first token is eos or that the row does not hold whole.
+ * Triple p = tok0 << 42 | tok1 << 21 | tok2 (raw tokens, each < 2^21).  cap = (row_len - 1) / 3.
+ *   canon[B, cap]  the row's p in ascending order, duplicates kept, then -1
+ *   n[B]           triples in the list            nset[B]  distinct triples
+ *   key[B, 2]      for seed s in (ARK_GRAPH_KEY_SEED0, _SEED1): h = s; h = mix(h ^ p) over the sorted list in order;
+ *                  h = mix(h ^ n); mix = the splitmix64 finaliser (x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *                  x *= 0x94D049BB133111EB; x ^= x >> 31).  A function of (n, sorted list) alone, stable across runs.
+ * cap <= 64: one wave per row; cap <= 1024: one workgroup per row; cap > 1024: ARK_ERR_SHAPE, nothing launched or written. */
+#define ARK_GRAPH_KEY_SEED0 0x9E3779B97F4A7C15ull
+#define ARK_GRAPH_KEY_SEED1 0xC2B2AE3D27D4EB4Full
+int ark_graph_canon(const int64_t* toks, int64_t ld, int B, int row_len, const int64_t* lens, int64_t eos, int64_t* canon,
+                    int* n, int* nset, int64_t* key, void* stream);
+/* Pairs of canonical graphs: for q < P, A = row ia[q] and B = row ib[q] of canon[rows, cap] with their n: inter[q] = distinct
+ * triples in both, da[q] / db[q] = distinct triples of A / B.  An index outside 0 .. rows - 1 gives -1 in all three. */
+int ark_graph_pair_stats(const int64_t* canon, const int* n, int rows, int cap, const int* ia, const int* ib, int P, int* inter,
+                         int* da, int* db, void* stream);
 
 /* ---- Transformer variant t-ARK (reference: DecoderOnlyTransformer, kgvae/model/models.py:349-366 = stock
  *      nn.TransformerEncoderLayer stack: post-norm, ReLU feed-forward, causal mask).  Rows are time-major (t, b);

@@ -14,6 +14,10 @@ directions, per anchor), builds all points of all walks, decodes them in ONE `de
 construction (line_points) and the statistics (flip_stats, jaccard_stats, overlap_stats) take latents and decoded triple
 sets, so they can be used on latents of one's own.
 
+`--device-stats` (device_stats=True of the smoothness score and the flip rate): the decoded tokens stay on the device, the
+graphs are compared there (ark_amd.graphs: canonical graphs and ark_graph_pair_stats over every walk's pairs) and only three
+integers per pair come back; the returned numbers are the same.
+
 Out of scope: the reference's two wd-movies figure functions (t-SNE of encoded test graphs, networkx drawings of an
 interpolation).  They need sklearn, matplotlib, networkx and the IntelliGraphs files, none of which this package depends on.
 `wandb` is optional, as in kgvae.experiments.train."""
@@ -130,6 +134,24 @@ def decode_walks(model, walks, steps, epsilon, beam):
     return [sets[w * (steps + 1):(w + 1) * (steps + 1)] for w in range(len(walks))]
 
 
+def walk_pair_counts(model, walks, steps, epsilon, beam):
+    """the device form of decode_walks: all points of all walks in ONE per-latent decode whose tokens stay on the device
+    (SAIL.decode_latent_tokens), canonical graphs (ark_amd.graphs.canon) and ONE pair_stats call over every walk's
+    (step, previous) and (step, anchor) pairs.  -> per walk, per step ((inter, d_step, d_previous), (inter, d_step,
+    d_anchor)): distinct triples in common and on either side, as Python ints"""
+    from ark_amd import graphs
+    model_unwrapped = _unwrap(model)
+    seq_len, special_tokens, _, _ = _codec(model_unwrapped)
+    pts = torch.cat([line_points(z0, direction, steps, epsilon) for z0, direction in walks])
+    toks, lens = model_unwrapped.decode_latent_tokens(pts, seq_len, special_tokens, beam=beam, per_latent=True)
+    batch = graphs.canon(toks, lens, eos=special_tokens["EOS"], vocab=model_unwrapped.config["vocab_size"])
+    ia, ib = graphs.walk_pairs(len(walks), steps)
+    inter, da, db = (x.tolist() for x in graphs.pair_stats(batch, ia, ib))
+    trip = list(zip(inter, da, db))
+    half = len(walks) * steps
+    return [list(zip(trip[w * steps:(w + 1) * steps], trip[half + w * steps:half + (w + 1) * steps])) for w in range(len(walks))]
+
+
 # ---------------------------------------------------------------------------------------------------- checkpoint
 def load_model(checkpoint_dir, dataset, model_type, epoch=None, device=None):
     """-> (model in eval mode, its config, the checkpoint's path, vocabularies, dataset_meta) from
@@ -220,9 +242,10 @@ def smoothness_line_check_autoreg(model, i2e, i2r, steps: int = 10, epsilon: flo
 
 @torch.no_grad()
 def latent_smoothness_score_autoreg(model, steps: int = 10, epsilon: float = 0.1, n_anchors: int = 3, n_dirs: int = 3, beam: int = 3,
-                                    device: str = None):
+                                    device: str = None, device_stats: bool = False):
     """-> (average Jaccard between consecutive steps, average Jaccard between each step and its anchor) over n_anchors x
-    n_dirs walks of `steps` steps"""
+    n_dirs walks of `steps` steps.  device_stats: the decoded tokens stay on the device and the set sizes come from
+    ark_graph_pair_stats (walk_pair_counts); the same numbers"""
     model_unwrapped = _unwrap(model)
     if device is None:
         device = next(model_unwrapped.parameters()).device
@@ -230,8 +253,13 @@ def latent_smoothness_score_autoreg(model, steps: int = 10, epsilon: float = 0.1
     total_local = total_global = 0.0
     count = 0
     if walks and steps > 0:
-        for sets in decode_walks(model_unwrapped, walks, steps, epsilon, beam):
-            for local, glob in jaccard_stats(sets):          # (summed step by step, in the reference's order)
+        if device_stats:
+            from ark_amd.graphs import jaccard_stats_from_counts
+            per_walk = [jaccard_stats_from_counts(*zip(*w)) for w in walk_pair_counts(model_unwrapped, walks, steps, epsilon, beam)]
+        else:
+            per_walk = [jaccard_stats(sets) for sets in decode_walks(model_unwrapped, walks, steps, epsilon, beam)]
+        for stats in per_walk:
+            for local, glob in stats:          # (summed step by step, in the reference's order)
                 total_local += local
                 total_global += glob
                 count += 1
@@ -245,9 +273,9 @@ def latent_smoothness_score_autoreg(model, steps: int = 10, epsilon: float = 0.1
 
 @torch.no_grad()
 def latent_flip_rate_autoreg(model, steps: int = 30, epsilon: float = 0.05, n_anchors: int = 5, n_dirs: int = 4, beam: int = 3,
-                             device: str = None):
+                             device: str = None, device_stats: bool = False):
     """-> (fraction of steps that change the decoded graph, average number of consecutive points with the same graph) over
-    n_anchors x n_dirs walks of `steps` steps"""
+    n_anchors x n_dirs walks of `steps` steps.  device_stats: as in latent_smoothness_score_autoreg"""
     model_unwrapped = _unwrap(model)
     if device is None:
         device = next(model_unwrapped.parameters()).device
@@ -255,10 +283,15 @@ def latent_flip_rate_autoreg(model, steps: int = 30, epsilon: float = 0.05, n_an
     total_flips = total_steps = 0
     all_basin_lengths = []
     if walks:
-        for sets in decode_walks(model_unwrapped, walks, steps, epsilon, beam):
-            flips, basins = flip_stats(sets)
+        if device_stats and steps > 0:
+            from ark_amd.graphs import flip_stats_from_equal, sets_equal
+            per_walk = [flip_stats_from_equal([sets_equal(*prev) for prev, _ in w])
+                        for w in walk_pair_counts(model_unwrapped, walks, steps, epsilon, beam)]
+        else:
+            per_walk = [flip_stats(sets) for sets in decode_walks(model_unwrapped, walks, steps, epsilon, beam)]
+        for flips, basins in per_walk:
             total_flips += flips
-            total_steps += len(sets) - 1
+            total_steps += steps
             all_basin_lengths += basins
     flip_rate = total_flips / max(1, total_steps)
     avg_basin = sum(all_basin_lengths) / max(1, len(all_basin_lengths))
@@ -278,6 +311,8 @@ def main(argv=None):
     parser.add_argument('--directions', type=int, default=20)
     parser.add_argument('--epsilon', type=float, default=0.1)
     parser.add_argument('--epoch', type=int, default=None, help='If set, load that epoch; else load best')
+    parser.add_argument('--device-stats', action='store_true',
+                        help='smoothness score and flip rate from graph keys computed on the device (same numbers)')
     args = parser.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("kgvae.experiments.interpolation needs an AMD GPU: the model runs on hand-written gfx950 kernels only")
@@ -311,8 +346,10 @@ def main(argv=None):
         print("----------------------------------------------------------------------")
         random_steps_latent_autoreg(model, i2e=i2e, i2r=i2r, n_directions=args.directions, epsilon=e, device=device)
         smoothness_line_check_autoreg(model, i2e=i2e, i2r=i2r, steps=10, epsilon=e, device=device, beam=beam)
-        latent_smoothness_score_autoreg(model, steps=10, epsilon=e, n_anchors=3, n_dirs=3, beam=beam, device=device)
-        latent_flip_rate_autoreg(model, steps=30, epsilon=e, n_anchors=5, n_dirs=4, beam=beam, device=device)
+        latent_smoothness_score_autoreg(model, steps=10, epsilon=e, n_anchors=3, n_dirs=3, beam=beam, device=device,
+                                        device_stats=args.device_stats)
+        latent_flip_rate_autoreg(model, steps=30, epsilon=e, n_anchors=5, n_dirs=4, beam=beam, device=device,
+                                 device_stats=args.device_stats)
     if wandb is not None:
         wandb.finish()
     return 0

@@ -15,7 +15,8 @@ Differences that are deliberate:
     configs/autoreg_syn-paths.yaml:35-36) continue a run from a checkpoint this module wrote;
   * extra optional keys: precision (mixed|bf16|f16|f32), synthetic_sizes, max_steps_per_epoch,
     permute_rng (python|numpy), seed (data-parallel runs are always seeded: every rank must build the same model
-    and draw the same epoch order).
+    and draw the same epoch order), device_graph_stats (log generation/unique_rate and generation/novel_rate every
+    verify_every epochs from graph keys computed on the device, with or without a verifier).
 """
 import argparse
 import json
@@ -378,6 +379,13 @@ def main(argv=None):
         if main_rank:
             print(f"Resumed from {config['checkpoint_path']} at epoch {start_epoch}")
 
+    device_graph_stats = bool(config.get("device_graph_stats", False))
+    train_keys = None
+    if device_graph_stats and main_rank:
+        # keys of the training split's graphs, once: built from the stored triples, no permutation drawn, no generator touched
+        from ark_amd import graphs as graphkeys
+        train_keys = graphkeys.dataset_keys(train_ds, device)
+
     for epoch in range(start_epoch, num_epochs):
         if main_rank:
             print(f"\nEpoch {epoch + 1}/{num_epochs}")
@@ -427,6 +435,16 @@ def main(argv=None):
             tracker.log({"verification/validity_rate": res.get("semantics", 0.0) / 100.0,
                          "verification/novelty_rate": res.get("novel", 0.0) / 100.0,
                          "verification/valid_novelty_rate": res.get("novel_semantics", 0.0) / 100.0})
+        if device_graph_stats and (epoch + 1) % config.get("verify_every", 10) == 0:
+            # id-level uniqueness and novelty of generated graphs; the tokens never leave the device (needs no rule checker)
+            target_n = config.get("num_generated_latent_graphs", 1000)
+            if model_type in ("SAIL", "t-SAIL"):
+                gs = model.graph_stats(target_n, seq_len, special_tokens, beam=1, train_keys=train_keys)
+            else:
+                gs = model.graph_stats(target_n, seq_len, special_tokens, train_keys=train_keys, sample=True,
+                                       temperature=config.get("temperature", 1.0), top_p=config.get("top_p", 0.9),
+                                       top_k=config.get("top_k", 0), sampler=config.get("ark_sampler", "torch"))
+            tracker.log({"generation/unique_rate": gs["unique_rate"], "generation/novel_rate": gs["novel_rate"]})
         tracker.log(log)
         print(f"Train Loss: {train_loss:.4f} (Recon: {train_recon:.4f})  [{log['train/graphs_per_sec']:.0f} graphs/s]")
         print(f"Val   Loss: {val_loss:.4f} (Recon: {val_recon:.4f})")

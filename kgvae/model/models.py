@@ -280,6 +280,62 @@ class SAIL(_EngineModel):
         return _pad_eos(toks, seq_len, eos)
 
     @torch.no_grad()
+    def decode_latent_tokens(self, z, seq_len, special_tokens, beam=4, per_latent=False):
+        """the token rows decode_latent parses, left on the device: -> (toks [B, <= seq_len] int64, lens [B] int64 or None).
+        per_latent: every latent its own beam (Engine.beam_decode_rows), row b holds lens[b] tokens and EOS past them;
+        otherwise greedy (beam 1) or the reference's batch-shared beam, whole rows (lens None)."""
+        self.eval()
+        eng = self.engine()
+        z = z.to(next(self.parameters()).device, dtype=torch.float32)
+        kw = dict(max_len=seq_len - 1, bos=special_tokens["BOS"], eos=special_tokens["EOS"])
+        if per_latent:
+            return eng.beam_decode_rows(z, beam, **kw)
+        return (eng.greedy_decode(z, **kw) if beam == 1 else eng.beam_decode(z, beam, **kw)), None
+
+    @torch.no_grad()
+    def graph_stats(self, num_samples, seq_len, special_tokens, beam=1, per_latent=False, train_keys=None, z=None):
+        """uniqueness (and, with the training split's keys, novelty) of the graphs decoded from num_samples latents
+        z ~ N(0, I) (or the rows of `z`), without the tokens leaving the device: decode_latent_tokens -> ark_amd.graphs.canon ->
+        a few integer ops on the keys.  -> {"n", "unique", "unique_rate", ["novel", "novel_rate",] "empty", "mean_triples"}.
+        `unique` is len(count_unique_graphs(...)) for the same latents.  A graph is novel when canonical_graph_string of its
+        id triples is not a training graph's (`train_keys` = ark_amd.graphs.dataset_keys(train split)): the id-level
+        definition, not IntelliGraphs' label-level number (which first drops triples with unknown ids)."""
+        from ark_amd import graphs
+        if z is None:
+            z = torch.randn((num_samples, self.config["d_latent"]), device=next(self.parameters()).device)
+        toks, lens = self.decode_latent_tokens(z, seq_len, special_tokens, beam=beam, per_latent=per_latent)
+        batch = graphs.canon(toks, lens, eos=special_tokens["EOS"], vocab=self.config["vocab_size"])
+        return graphs.summary(batch, train_keys)
+
+    def _triple_keys(self, triples, special_tokens):
+        """keys of the input graphs `triples` [B, T, 3] (id triples on the device; padding triples, whose head is pad_eid,
+        come last and are not part of the graph)"""
+        from ark_amd import graphs
+        c = self.config
+        B, T = triples.shape[0], triples.shape[1]
+        offs = torch.tensor([c["ENT_BASE"], c["REL_BASE"], c["ENT_BASE"]], dtype=torch.int64, device=triples.device)
+        rows = torch.full((B, 3 * T + 2), special_tokens["EOS"], dtype=torch.int64, device=triples.device)
+        rows[:, 0] = special_tokens["BOS"]
+        rows[:, 1:3 * T + 1] = (triples.to(torch.int64) + offs).reshape(B, 3 * T)
+        count = torch.full((B,), T, dtype=torch.int64, device=triples.device)
+        if c.get("pad_eid") is not None:
+            count = (triples[:, :, 0] != c["pad_eid"]).sum(dim=1)
+        return graphs.canon(rows, 3 * count + 1, eos=special_tokens["EOS"], vocab=c["vocab_size"]).key
+
+    @torch.no_grad()
+    def reconstruction_rate(self, triples, seq_len, special_tokens, beam=4, eps=None):
+        """share of the graphs `triples` [B, T, 3] that come back from encode -> decode (beam_generate's decode: greedy at
+        beam 1, else the batch-shared beam) as the same graph: the decoded row's key equals the input graph's.  The device
+        form of comparing generate_test_graphs' output with its input, graph by graph."""
+        from ark_amd import graphs
+        triples = triples.to(next(self.parameters()).device)
+        z, _, _ = self.encode(triples, eps)
+        toks, lens = self.decode_latent_tokens(z, seq_len, special_tokens, beam=beam)
+        out = graphs.canon(toks, lens, eos=special_tokens["EOS"], vocab=self.config["vocab_size"]).key
+        same = (out == self._triple_keys(triples, special_tokens)).all(dim=1)
+        return float(same.double().mean())
+
+    @torch.no_grad()
     def count_unique_graphs(self, latent_dim, decode_latent_fn, num_samples=1000, beam=1):
         self.eval()
         zs = torch.randn((num_samples, latent_dim), device=next(self.parameters()).device)
@@ -443,6 +499,23 @@ class ARK(_EngineModel):
             fill = torch.full((B, seq_len - seq.size(1)), eos, dtype=torch.long, device=device)
             seq = torch.cat([seq, fill], dim=1)
         return seq[:, :seq_len]
+
+    @torch.no_grad()
+    def graph_stats(self, num_samples, seq_len, special_tokens, train_keys=None, batch_size=None, **sampling):
+        """uniqueness (and, with the training split's keys, novelty) of num_samples generated graphs, the tokens staying on
+        the device: generate(**sampling) in batches of batch_size (default: one batch) -> ark_amd.graphs.canon -> a few
+        integer ops on the keys.  Same entries and the same id-level novelty as SAIL.graph_stats.  With the fused sampler
+        and a seed, batch i draws with seed + i."""
+        from ark_amd import graphs
+        bs = int(batch_size or num_samples)
+        seed = sampling.pop("seed", None)
+        chunks = []
+        for i, i0 in enumerate(range(0, num_samples, bs)):
+            kw = dict(sampling, seed=seed + i) if seed is not None else sampling
+            chunks.append(self.generate(seq_len, special_tokens, batch_size=min(bs, num_samples - i0), **kw))
+        toks = chunks[0] if len(chunks) == 1 else torch.cat(chunks, 0)
+        batch = graphs.canon(toks, None, eos=special_tokens["EOS"], vocab=self.config["vocab_size"])
+        return graphs.summary(batch, train_keys)
 
     @torch.no_grad()
     def posterior_bits(self, dataset, device, pad_id=0, sample_frac=0.1, desc="Posterior compression", batch_size=256):
