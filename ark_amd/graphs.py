@@ -4,7 +4,9 @@ row on the host, for whole batches of token rows that stay on the device.
     canon(toks, lens, eos)        -> GraphBatch(canon, n, nset, key)      ark_graph_canon
     unique_count / unique_mask / novel_mask                                a few torch ops on the [N, 2] keys
     pair_stats(batch, ia, ib)     -> (inter, da, db) int32                 ark_graph_pair_stats
-    dataset_keys(dataset, device) -> keys of a GraphSeqDataset split
+    dataset_keys(dataset, device) -> keys of a GraphSeqDataset split; dataset_canon(...) -> its GraphBatch
+    nearest(queries, refs)        -> Nearest(idx, inter, dq, dr) int32     ark_graph_nearest: the reference with the largest
+                                     Jaccard index per query; jaccard_tensor / nearest_summary turn it into numbers
 
 Two rows have the same key exactly when `canonical_graph_string` of their parsed graphs is the same string (up to a 2^-128
 collision of the two 64-bit folds): the key is a function of the sorted list of triples, duplicates kept.  The key's
@@ -14,6 +16,7 @@ The integer-to-number derivations (jaccard_from_counts, flip_stats_from_equal, o
 three integers of a pair, written so that they return bit for bit what kgvae.experiments.interpolation's jaccard /
 flip_stats / jaccard_stats / overlap_stats return on the sets themselves.  This module depends on the library only, not on
 an engine."""
+import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -218,8 +221,98 @@ def dataset_keys(dataset, device, chunk=16384):
     return torch.cat(out) if out else torch.empty(0, 2, dtype=torch.int64, device=device)
 
 
-def summary(batch, train_keys=None):
-    """the statistics of a batch of generated graphs (one host read)"""
+def dataset_canon(dataset, device, chunk=16384):
+    """GraphBatch of the graphs of a GraphSeqDataset split, on `device`: the sibling of dataset_keys that keeps the sorted
+    lists (what `nearest` compares against).  Built from dataset_rows: no permutation is drawn and no generator is touched.
+    Chunks whose rows differ in width are padded with -1 to one cap."""
+    n = len(dataset)
+    eos = dataset.special_tokens["EOS"]
+    parts = []
+    for i0 in range(0, n, chunk):
+        rows, lens = dataset_rows(dataset, np.arange(i0, min(n, i0 + chunk)))
+        vocab = int(rows.max()) + 1
+        parts.append(canon(torch.from_numpy(rows).to(device), torch.from_numpy(lens).to(device), eos=eos, vocab=vocab))
+    if not parts:
+        return GraphBatch(torch.empty(0, 0, dtype=torch.int64, device=device), torch.empty(0, dtype=torch.int32, device=device),
+                          torch.empty(0, dtype=torch.int32, device=device), torch.empty(0, 2, dtype=torch.int64, device=device))
+    cap = max(p.canon.shape[1] for p in parts)
+    lists = [p.canon if p.canon.shape[1] == cap else torch.nn.functional.pad(p.canon, (0, cap - p.canon.shape[1]), value=-1)
+             for p in parts]
+    return GraphBatch(torch.cat(lists), torch.cat([p.n for p in parts]), torch.cat([p.nset for p in parts]),
+                      torch.cat([p.key for p in parts]))
+
+
+# ------------------------------------------------------------------------------------------- the nearest graph of another batch
+Nearest = namedtuple("Nearest", "idx inter dq dr")
+
+
+def nearest_raw(queries, refs, exclude_self, strips, idx, inter, dq, dr):
+    """ark_graph_nearest on the current stream into caller-owned outputs (its scratch is allocated here); returns the
+    library's code (0, or ARK_ERR_*)"""
+    qc, rc = queries.canon.contiguous(), refs.canon.contiguous()
+    qn, rn = queries.n.contiguous(), refs.n.contiguous()
+    NQ, NR, capq, capr = qc.shape[0], rc.shape[0], qc.shape[1], rc.shape[1]
+    size = L.lib().ark_graph_nearest_scratch_bytes
+    size.restype = ctypes.c_long
+    nbytes = int(size(L.i32(NQ), L.i32(NR), L.i32(capq), L.i32(capr), L.i32(strips)))
+    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=qc.device) if nbytes else None
+    return int(L.lib().ark_graph_nearest(L.ptr(qc), L.ptr(qn), L.i32(NQ), L.i32(capq), L.ptr(rc), L.ptr(rn), L.i32(NR),
+                                         L.i32(capr), L.i32(1 if exclude_self else 0), L.i32(strips), L.ptr(idx), L.ptr(inter),
+                                         L.ptr(dq), L.ptr(dr), L.ptr(scratch), L.i64(nbytes), L.cur_stream()))
+
+
+def nearest(queries, refs, exclude_self=False, strips=0):
+    """for every graph of `queries` the graph of `refs` (two GraphBatches on one device; their caps may differ) with the
+    largest Jaccard index over the sets of distinct triples -> Nearest(idx, inter, dq, dr), int32 [NQ] on the device:
+    the reference's row (the lowest among equally near ones), |Q & R|, |Q|, |R|.  J follows jaccard_from_counts: 1 for two
+    empty graphs, 0 when exactly one is empty; fractions are compared exactly.  exclude_self: row q of `refs` is skipped
+    for query q (a batch against itself).  A query without an admissible reference gets idx = inter = dr = -1.  `strips`
+    forces the split of the reference axis (0: chosen by the library); the result does not depend on it."""
+    dev = queries.canon.device
+    NQ = int(queries.n.numel())
+    if max(queries.canon.shape[1], refs.canon.shape[1]) > 1024:
+        raise L.ArkError("nearest: a graph list holds at most 1024 triples")
+    if refs.canon.device != dev:
+        raise L.ArkError("nearest: queries and references live on different devices")
+    out = Nearest(*(torch.empty(NQ, dtype=torch.int32, device=dev) for _ in range(4)))
+    if NQ == 0:
+        return out
+    L.check(nearest_raw(queries, refs, exclude_self, strips, *out), "ark_graph_nearest")
+    return out
+
+
+def jaccard_tensor(near):
+    """float64 [NQ] on the device: jaccard_from_counts of every row of a Nearest; NaN where idx == -1"""
+    inter, dq, dr = near.inter.double(), near.dq.double(), near.dr.double()
+    union = dq + dr - inter
+    j = torch.where(union == 0, torch.ones_like(union), inter / union.clamp(min=1.0))
+    return torch.where(near.idx < 0, torch.full_like(j, float("nan")), j)
+
+
+def nearest_summary(near):
+    """the statistics of a Nearest (one host read): {"n": rows with a nearest reference, "mean_jaccard": their mean J (NaN
+    without any), "hist": 11 counts, "copied": hist[10], "copied_rate": copied / n}.  The bin of a row is computed on the
+    integers: 10 when J = 1, else (10 * inter) // (dq + dr - inter), so bin b < 10 holds b / 10 <= J < (b + 1) / 10.
+    `copied` counts SET equality of the distinct triples; key equality (novel_mask) also tells duplicate triples apart, so a
+    generated graph that repeats a triple of a training graph is copied here and novel there."""
+    ok = near.idx >= 0
+    inter, dq, dr = near.inter.long(), near.dq.long(), near.dr.long()
+    union = dq + dr - inter
+    bins = torch.where(union == 0, torch.full_like(union, 10), (10 * inter) // union.clamp(min=1))
+    hist = torch.bincount(bins[ok], minlength=11)[:11].double()
+    j = jaccard_tensor(near)
+    vals = torch.cat([ok.sum().double().view(1), torch.where(ok, j, torch.zeros_like(j)).sum().view(1), hist]).tolist()
+    n = int(vals[0])
+    hist = [int(v) for v in vals[2:]]
+    return {"n": n, "mean_jaccard": vals[1] / n if n else float("nan"), "hist": hist, "copied": hist[10],
+            "copied_rate": hist[10] / max(1, n)}
+
+
+def summary(batch, train_keys=None, train_graphs=None, diversity=False):
+    """the statistics of a batch of generated graphs.  With `train_graphs` (a GraphBatch, e.g. dataset_canon(train split)) also
+    how near the batch is to it: nearest_train_jaccard (the mean J of every graph's nearest training graph),
+    nearest_train_hist (11 bins of it) and copied_rate (nearest_summary); with `diversity` nearest_other_jaccard, the mean J
+    of every graph's nearest OTHER graph of the batch."""
     N = int(batch.n.numel())
     uniq = unique_count(batch)
     head = torch.stack([(batch.n == 0).sum().double(), batch.n.double().sum()])
@@ -232,4 +325,11 @@ def summary(batch, train_keys=None):
         out["novel_rate"] = int(vals[2]) / max(1, N)
     out["empty"] = int(vals[0])
     out["mean_triples"] = vals[1] / max(1, N)
+    if train_graphs is not None:
+        ns = nearest_summary(nearest(batch, train_graphs))
+        out["nearest_train_jaccard"] = ns["mean_jaccard"]
+        out["nearest_train_hist"] = ns["hist"]
+        out["copied_rate"] = ns["copied_rate"]
+    if diversity:
+        out["nearest_other_jaccard"] = nearest_summary(nearest(batch, batch, exclude_self=True))["mean_jaccard"]
     return out

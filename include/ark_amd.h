@@ -471,6 +471,24 @@ int ark_graph_canon(const int64_t* toks, int64_t ld, int B, int row_len, const i
  * triples in both, da[q] / db[q] = distinct triples of A / B.  An index outside 0 .. rows - 1 gives -1 in all three. */
 int ark_graph_pair_stats(const int64_t* canon, const int* n, int rows, int cap, const int* ia, const int* ib, int P, int* inter,
                          int* da, int* db, void* stream);
+/* Nearest reference graph.  Queries qcanon[NQ, capq] with qn[NQ], references rcanon[NR, capr] with rn[NR]: both exactly what
+ * ark_graph_canon writes (ascending as unsigned values, duplicates kept, -1 past n; n is clipped into 0 .. cap and nothing past
+ * it is read); capq and capr may differ.  Over the sets of distinct triples of a pair, inter = |Q & R|, dq = |Q|, dr = |R| and
+ * J = 1 when both are empty, else inter / (dq + dr - inter) (so 0 when exactly one is empty).  For every query q:
+ *   idx[q]    the reference with the largest J, fractions compared exactly by integer cross-multiplication, the LOWEST index
+ *             among equal J; with exclude_self != 0 the pair r == q is skipped (a set against itself)
+ *   inter[q], dr[q]   the two counts of that pair        dq[q]   the query's distinct triples
+ * A query with no admissible reference (NR == 0, or NR == 1 with exclude_self and q == 0) gets idx = inter = dr = -1, dq
+ * still filled.  Both caps <= 64: one lane per pair (lists in registers up to cap 8, in LDS with a linear merge above);
+ * otherwise one wave per reference row against a tile of queries in LDS.
+ * The reference axis is cut into `strips` strips (0: chosen by the library; at most min(NR, 1024)) whose winners a second
+ * launch merges: the outputs do not depend on strips.  scratch: ark_graph_nearest_scratch_bytes(...) bytes for the same
+ * sizes and strips (0 bytes when one strip is used; then scratch may be null).  ARK_ERR_SHAPE for a cap above 1024,
+ * ARK_ERR_ARG for null pointers, NQ <= 0, NR < 0 or a scratch that is too small; then nothing is launched or written. */
+long ark_graph_nearest_scratch_bytes(int NQ, int NR, int capq, int capr, int strips);
+int ark_graph_nearest(const int64_t* qcanon, const int* qn, int NQ, int capq, const int64_t* rcanon, const int* rn, int NR,
+                      int capr, int exclude_self, int strips, int* idx, int* inter, int* dq, int* dr, void* scratch,
+                      int64_t scratch_bytes, void* stream);
 
 /* ---- Transformer variant t-ARK (reference: DecoderOnlyTransformer, kgvae/model/models.py:349-366 = stock
  *      nn.TransformerEncoderLayer stack: post-norm, ReLU feed-forward, causal mask).  Rows are time-major (t, b);

@@ -16,7 +16,9 @@ Differences that are deliberate:
   * extra optional keys: precision (mixed|bf16|f16|f32), synthetic_sizes, max_steps_per_epoch,
     permute_rng (python|numpy), seed (data-parallel runs are always seeded: every rank must build the same model
     and draw the same epoch order), device_graph_stats (log generation/unique_rate and generation/novel_rate every
-    verify_every epochs from graph keys computed on the device, with or without a verifier).
+    verify_every epochs from graph keys computed on the device, with or without a verifier), device_graph_nearest (only
+    together with device_graph_stats: also log generation/nearest_train_jaccard and generation/copied_rate, every generated
+    graph against its nearest training graph, ark_amd.graphs.nearest).
 """
 import argparse
 import json
@@ -380,11 +382,17 @@ def main(argv=None):
             print(f"Resumed from {config['checkpoint_path']} at epoch {start_epoch}")
 
     device_graph_stats = bool(config.get("device_graph_stats", False))
-    train_keys = None
+    device_graph_nearest = device_graph_stats and bool(config.get("device_graph_nearest", False))
+    train_keys = train_graphs = None
     if device_graph_stats and main_rank:
         # keys of the training split's graphs, once: built from the stored triples, no permutation drawn, no generator touched
         from ark_amd import graphs as graphkeys
-        train_keys = graphkeys.dataset_keys(train_ds, device)
+        if device_graph_nearest:
+            # the sorted lists too: every generated graph is compared with every training graph (ark_amd.graphs.nearest)
+            train_graphs = graphkeys.dataset_canon(train_ds, device)
+            train_keys = train_graphs.key
+        else:
+            train_keys = graphkeys.dataset_keys(train_ds, device)
 
     for epoch in range(start_epoch, num_epochs):
         if main_rank:
@@ -439,12 +447,17 @@ def main(argv=None):
             # id-level uniqueness and novelty of generated graphs; the tokens never leave the device (needs no rule checker)
             target_n = config.get("num_generated_latent_graphs", 1000)
             if model_type in ("SAIL", "t-SAIL"):
-                gs = model.graph_stats(target_n, seq_len, special_tokens, beam=1, train_keys=train_keys)
+                gs = model.graph_stats(target_n, seq_len, special_tokens, beam=1, train_keys=train_keys, train_graphs=train_graphs)
             else:
-                gs = model.graph_stats(target_n, seq_len, special_tokens, train_keys=train_keys, sample=True,
+                gs = model.graph_stats(target_n, seq_len, special_tokens, train_keys=train_keys, train_graphs=train_graphs,
+                                       sample=True,
                                        temperature=config.get("temperature", 1.0), top_p=config.get("top_p", 0.9),
                                        top_k=config.get("top_k", 0), sampler=config.get("ark_sampler", "torch"))
-            tracker.log({"generation/unique_rate": gs["unique_rate"], "generation/novel_rate": gs["novel_rate"]})
+            rates = {"generation/unique_rate": gs["unique_rate"], "generation/novel_rate": gs["novel_rate"]}
+            if train_graphs is not None:
+                rates["generation/nearest_train_jaccard"] = gs["nearest_train_jaccard"]
+                rates["generation/copied_rate"] = gs["copied_rate"]
+            tracker.log(rates)
         tracker.log(log)
         print(f"Train Loss: {train_loss:.4f} (Recon: {train_recon:.4f})  [{log['train/graphs_per_sec']:.0f} graphs/s]")
         print(f"Val   Loss: {val_loss:.4f} (Recon: {val_recon:.4f})")

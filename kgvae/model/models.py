@@ -293,19 +293,23 @@ class SAIL(_EngineModel):
         return (eng.greedy_decode(z, **kw) if beam == 1 else eng.beam_decode(z, beam, **kw)), None
 
     @torch.no_grad()
-    def graph_stats(self, num_samples, seq_len, special_tokens, beam=1, per_latent=False, train_keys=None, z=None):
+    def graph_stats(self, num_samples, seq_len, special_tokens, beam=1, per_latent=False, train_keys=None, z=None,
+                    train_graphs=None, diversity=False):
         """uniqueness (and, with the training split's keys, novelty) of the graphs decoded from num_samples latents
         z ~ N(0, I) (or the rows of `z`), without the tokens leaving the device: decode_latent_tokens -> ark_amd.graphs.canon ->
         a few integer ops on the keys.  -> {"n", "unique", "unique_rate", ["novel", "novel_rate",] "empty", "mean_triples"}.
         `unique` is len(count_unique_graphs(...)) for the same latents.  A graph is novel when canonical_graph_string of its
         id triples is not a training graph's (`train_keys` = ark_amd.graphs.dataset_keys(train split)): the id-level
-        definition, not IntelliGraphs' label-level number (which first drops triples with unknown ids)."""
+        definition, not IntelliGraphs' label-level number (which first drops triples with unknown ids).  With `train_graphs`
+        (ark_amd.graphs.dataset_canon(train split)) the dict gains nearest_train_jaccard, nearest_train_hist and copied_rate:
+        how near every graph is to its nearest training graph (ark_amd.graphs.nearest); with `diversity`
+        nearest_other_jaccard, the same against the other decoded graphs."""
         from ark_amd import graphs
         if z is None:
             z = torch.randn((num_samples, self.config["d_latent"]), device=next(self.parameters()).device)
         toks, lens = self.decode_latent_tokens(z, seq_len, special_tokens, beam=beam, per_latent=per_latent)
         batch = graphs.canon(toks, lens, eos=special_tokens["EOS"], vocab=self.config["vocab_size"])
-        return graphs.summary(batch, train_keys)
+        return graphs.summary(batch, train_keys, train_graphs=train_graphs, diversity=diversity)
 
     def _triple_keys(self, triples, special_tokens):
         """keys of the input graphs `triples` [B, T, 3] (id triples on the device; padding triples, whose head is pad_eid,
@@ -501,11 +505,12 @@ class ARK(_EngineModel):
         return seq[:, :seq_len]
 
     @torch.no_grad()
-    def graph_stats(self, num_samples, seq_len, special_tokens, train_keys=None, batch_size=None, **sampling):
+    def graph_stats(self, num_samples, seq_len, special_tokens, train_keys=None, batch_size=None, train_graphs=None,
+                    diversity=False, **sampling):
         """uniqueness (and, with the training split's keys, novelty) of num_samples generated graphs, the tokens staying on
         the device: generate(**sampling) in batches of batch_size (default: one batch) -> ark_amd.graphs.canon -> a few
         integer ops on the keys.  Same entries and the same id-level novelty as SAIL.graph_stats.  With the fused sampler
-        and a seed, batch i draws with seed + i."""
+        and a seed, batch i draws with seed + i.  `train_graphs` and `diversity` as in SAIL.graph_stats."""
         from ark_amd import graphs
         bs = int(batch_size or num_samples)
         seed = sampling.pop("seed", None)
@@ -515,7 +520,7 @@ class ARK(_EngineModel):
             chunks.append(self.generate(seq_len, special_tokens, batch_size=min(bs, num_samples - i0), **kw))
         toks = chunks[0] if len(chunks) == 1 else torch.cat(chunks, 0)
         batch = graphs.canon(toks, None, eos=special_tokens["EOS"], vocab=self.config["vocab_size"])
-        return graphs.summary(batch, train_keys)
+        return graphs.summary(batch, train_keys, train_graphs=train_graphs, diversity=diversity)
 
     @torch.no_grad()
     def posterior_bits(self, dataset, device, pad_id=0, sample_frac=0.1, desc="Posterior compression", batch_size=256):
